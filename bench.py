@@ -20,7 +20,18 @@ ps_amd/bench_configs.py).
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; W untimed steps, then
 exactly K timed steps bracketed by barrier + cuda.synchronize on both sides; the max
-elapsed over ranks is used; rank 0 prints ONE JSON line.
+elapsed over ranks is used; rank 0 prints ONE JSON line.  Such a plain run does nothing else.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed step computed
+(its loss, its logits where the config has them, and the parameters and buffers the PS round left
+in the model) as ``DIR/<name>.npy`` in float32, at most 64 MB in all: arrays past their share are
+a fixed, seeded sample of their elements.  Inputs and initial weights are seeded, so two builds
+can be compared output for output.
+
+``--full``: everything the benchmark measures after the timed region -- per-phase PS timing
+(``--timing``, default 3 steps at world > 1), the host-sync audit (``--sync-audit``, default 2
+steps for the sparse configs), the collective bandwidth probe at world > 1 (``--comm-probe``),
+the timed sharded checkpoint (``--checkpoint-dir``) and the torch profile (``--profile-steps``).
 """
 from __future__ import annotations
 
@@ -43,6 +54,13 @@ def parse():
                          "the fused HIP paths fall back to the torch module path)")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps: write what the last timed step computed as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all; larger arrays as a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the benchmark measures after the timed region: per-phase PS timing, "
+                         "host-sync audit, collective probe, checkpoint, torch profile (the options marked "
+                         "--full below); a run without it only sets up, warms up, times and reports")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="0 = config default")
     ap.add_argument("--seq-len", type=int, default=0, help="0 = config default")
     ap.add_argument("--image-size", type=int, default=224)
@@ -59,24 +77,36 @@ def parse():
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--dlrm-rows", type=int, default=1000000)
     ap.add_argument("--tiny", type=int, default=0, help="llama-onebit: tiny config (smoke only)")
-    ap.add_argument("--profile-steps", type=int, default=0, help="torch.profiler over N extra steps (rank 0)")
+    ap.add_argument("--profile-steps", type=int, default=0,
+                    help="--full: torch.profiler over N extra steps (rank 0)")
     ap.add_argument("--json-out", type=str, default="")
     ap.add_argument("--comm-probe", type=int, default=1,
-                    help="world > 1: after the timed region, measure RS / AG / AR bandwidth (ps_amd/parallel/"
+                    help="--full, world > 1: after the timed region, measure RS / AG / AR bandwidth (ps_amd/parallel/"
                          "comm_probe.py) and report it in the JSON config")
     ap.add_argument("--compute-priority", choices=["auto", "high", "normal"], default="auto",
                     help="stream priority of forward / backward (auto: high for ResNet-50 with one rank per GPU)")
-    ap.add_argument("--checkpoint-dir", type=str, default=os.environ.get("PS_AMD_CHECKPOINT_DIR", ""),
-                    help="after the timed region: one sharded checkpoint of every rank's server shard (timed, "
-                         "reported on stderr) -- utils/checkpoint.py")
+    ap.add_argument("--checkpoint-dir", type=str, default="",
+                    help="--full: after the timed region (default $PS_AMD_CHECKPOINT_DIR): one sharded checkpoint "
+                         "of every rank's server shard (timed, reported on stderr) -- utils/checkpoint.py")
     ap.add_argument("--sync-audit", type=int, default=-1,
-                    help="after the timed region: N steps under torch.cuda.set_sync_debug_mode('warn'), "
+                    help="--full: after the timed region, N steps under torch.cuda.set_sync_debug_mode('warn'), "
                          "reporting the host-synchronising torch ops per step (default 2 for the sparse "
                          "configs, 0 otherwise)")
     ap.add_argument("--timing", type=int, default=0,
-                    help="after the timed region: N more steps with per-phase device timing "
+                    help="--full: after the timed region, N more steps with per-phase device timing "
                          "(fwd+bwd / push / serve / pull / exposed comm) printed to stderr")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.full:
+        args.checkpoint_dir = args.checkpoint_dir or os.environ.get("PS_AMD_CHECKPOINT_DIR", "")
+    else:
+        asked = [o for o, on in (("--timing", args.timing > 0), ("--sync-audit", args.sync_audit > 0),
+                                 ("--profile-steps", args.profile_steps > 0),
+                                 ("--checkpoint-dir", bool(args.checkpoint_dir))) if on]
+        if asked:
+            ap.error(f"{' '.join(asked)} runs after the timed region: add --full")
+    if args.dump_outputs and args.config == "mlp-tcp":
+        ap.error("--dump-outputs: the mlp-tcp plumbing config trains in worker processes and returns no arrays")
+    return args
 
 
 def _stream_count(engine, prio: str, side: bool, cpu: bool) -> int:
@@ -200,11 +230,18 @@ def main():
         print(f"[bench] WARNING: the allocator grew by {grew_gb:.1f} GB ({alloc_timed} segments) inside the timed "
               f"region: the host ran far ahead of the GPU (PS_AMD_MAX_INFLIGHT=0?)", file=sys.stderr, flush=True)
     value = bench.samples_per_step * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        arrays = {"loss": loss}
+        if bench.outputs is not None:
+            arrays.update(bench.outputs())
+        n_files, n_bytes = BC.dump_outputs(args.dump_outputs, arrays)
+        print(f"[bench] wrote {n_files} arrays ({n_bytes / 2**20:.1f} MB) of the last timed step to "
+              f"{args.dump_outputs}", file=sys.stderr, flush=True)
     # after the timed region: per-phase PS timing (default 3 steps at world > 1, so the driver's
     # multi-GPU lines show how much of the push / pull the backward hides) and the collective
     # bandwidth curve of this node's RCCL / xGMI plane
     tsum = comm = None
-    n_timing = args.timing if args.timing else (3 if world > 1 else 0)
+    n_timing = (args.timing if args.timing else (3 if world > 1 else 0)) if args.full else 0
     if n_timing and getattr(bench.engine, "timing_summary", None) is not None:
         eng = bench.engine
         try:
@@ -226,7 +263,8 @@ def main():
         if rank == 0 and tsum:
             print("[bench-timing] " + json.dumps(tsum), file=sys.stderr, flush=True)
     audit = None
-    n_audit = args.sync_audit if args.sync_audit >= 0 else (2 if args.config in ("dlrm", "ctr-async") else 0)
+    n_audit = (args.sync_audit if args.sync_audit >= 0 else (2 if args.config in ("dlrm", "ctr-async") else 0)) \
+        if args.full else 0
     if n_audit and not cpu:
         import warnings
 
@@ -245,7 +283,7 @@ def main():
         except Exception as e:  # diagnostics only
             torch.cuda.set_sync_debug_mode(0)
             print(f"[bench-sync-audit] failed: {e!r}", file=sys.stderr, flush=True)
-    if world > 1 and args.comm_probe:
+    if args.full and world > 1 and args.comm_probe:
         from ps_amd.parallel.comm_probe import probe
 
         try:

@@ -42,6 +42,51 @@ class Bench:
     engine: object = None
     stats: Optional[Callable[[], Dict]] = None  # extra counters for the JSON line (read after timing)
     dtype: str = "bf16"  # compute dtype reported in the JSON line
+    outputs: Optional[Callable[[], Dict[str, torch.Tensor]]] = None  # what the last step left (--dump-outputs)
+
+
+DUMP_BYTES = 56 << 20  # payload of a dump: with the .npy headers it stays under 64 MB
+DUMP_MIN = 4096  # arrays up to this many elements are always written whole
+
+
+def model_outputs(model, last=None) -> Dict[str, torch.Tensor]:
+    """What a PS round leaves to the caller: the pulled parameters and the float buffers (BatchNorm
+    running statistics) of the model, plus the last step's logits where the config keeps them."""
+    out = {"param." + n: p for n, p in model.named_parameters()}
+    out.update({"buffer." + n: b for n, b in model.named_buffers() if b.is_floating_point()})
+    if last:
+        out.update(last)
+    return out
+
+
+def dump_outputs(path: str, arrays: Dict[str, torch.Tensor], budget: int = DUMP_BYTES):
+    """Write every array as ``path/<name>.npy`` in float32, ``budget`` bytes in all.  When they hold
+    more, the arrays of up to DUMP_MIN elements are written whole and every larger one as a 1-D
+    sample of the same fraction of its elements (logical order, indices drawn once from a generator
+    seeded by the array's name: the same elements in every run and every build).  -> (files, bytes)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    sizes = [t.numel() for t in arrays.values()]
+    frac = 1.0
+    if 4 * sum(sizes) > budget:
+        small = sum(n for n in sizes if n <= DUMP_MIN)
+        frac = (budget // 4 - small) / sum(n for n in sizes if n > DUMP_MIN)
+        assert 0.0 < frac < 1.0, (budget, small)
+    n_bytes = 0
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        n = t.numel()
+        if frac < 1.0 and n > DUMP_MIN:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, n, (max(1, int(n * frac)),), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().contiguous().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        n_bytes += a.nbytes
+    return len(arrays), n_bytes
 
 
 def setup_resnet50(args, tp, dev) -> Bench:
@@ -59,10 +104,13 @@ def setup_resnet50(args, tp, dev) -> Bench:
         memory_format=torch.channels_last), torch.randint(0, 1000, (B,), device=dev, generator=g))
         for _ in range(POOL)]
     it = _cycle(pool)
+    last = {}
 
     def step():
         x, y = next(it)
-        loss = F.cross_entropy(model(x).float(), y)
+        logits = model(x)
+        last["logits"] = logits.detach()
+        loss = F.cross_entropy(logits.float(), y)
         loss.backward()
         ps.finish_step()
         return loss
@@ -70,7 +118,8 @@ def setup_resnet50(args, tp, dev) -> Bench:
     return Bench(step, B, "samples/sec (whole node) ResNet-50 sync-BSP at 1/2/4/8 MI355X workers", "samples/s",
                  {"model": "ResNet-50", "global_batch": B * tp.world, "seq_len": None, "image_size": S,
                   "parallelism": f"ps-bsp-colocated-dp{tp.world}", "optimizer": upd.name,
-                  "bucket_mb": args.bucket_mb, "staleness": args.staleness, "fused_bn": bool(args.fused_bn)}, ps)
+                  "bucket_mb": args.bucket_mb, "staleness": args.staleness, "fused_bn": bool(args.fused_bn)}, ps,
+                 outputs=lambda: model_outputs(model, last))
 
 
 def async_or_pipelined(model, upd, tp, stale: int, args, use_async: bool = True):
@@ -122,7 +171,7 @@ def setup_bert_ssp(args, tp, dev) -> Bench:
     return Bench(step, B, "sequences/sec (whole node) BERT-base MLM async bounded-staleness s=1", "sequences/s",
                  {"model": "BERT-base", "global_batch": B * tp.world, "seq_len": S,
                   "parallelism": f"ps-ssp{stale}-{'async' if use_async else 'pipelined'}-dp{tp.world}",
-                  "optimizer": upd.name, **probe}, ps)
+                  "optimizer": upd.name, **probe}, ps, outputs=lambda: model_outputs(model))
 
 
 def setup_dlrm(args, tp, dev) -> Bench:
@@ -175,7 +224,8 @@ def setup_dlrm(args, tp, dev) -> Bench:
                   # row exchange path at W > 1: "plane" (IPC arenas, parallel/row_plane.py) or
                   # "collective" (RCCL all-to-alls); "local" at W = 1
                   "sparse_exchange": tbl.exchange, **({"sparse_exchange_info": tbl.exchange_info}
-                                                      if tbl.exchange_info else {})}, ps, stats)
+                                                      if tbl.exchange_info else {})}, ps, stats,
+                 outputs=lambda: model_outputs(model))
 
 
 def setup_llama_onebit(args, tp, dev) -> Bench:
@@ -224,7 +274,7 @@ def setup_llama_onebit(args, tp, dev) -> Bench:
                   "compression": (f"1-bit Adam: 1-bit momentum + error feedback, {warm} full-precision warm-up rounds, "
                                   f"variance refresh every {refresh}th round") if onebit
                   else "none (1 worker: nothing to push)"},
-                 ps)
+                 ps, outputs=lambda: model_outputs(model))
 
 
 def setup_ctr_async(args, tp, dev) -> Bench:
@@ -272,7 +322,7 @@ def setup_ctr_async(args, tp, dev) -> Bench:
                                "row_tables": "device-resident (csrc/async_rows_gpu.cpp)" if dev.type == "cuda"
                                else "host callbacks",
                                **{k: v for k, v in ps.info.items() if k == "remote_write_probe"}},
-                 _Engine(), dtype="fp32")
+                 _Engine(), dtype="fp32", outputs=lambda: model_outputs(model))
 
 
 SETUPS = {"resnet50": setup_resnet50, "bert-ssp": setup_bert_ssp, "dlrm": setup_dlrm,

@@ -5,8 +5,8 @@ Measures the three collectives the co-located PS issues -- reduce-scatter (push)
 one-shot forms of the first two (all-to-all over every peer link at once, owner-side sum: the
 ring-vs-direct comparison SURVEY §2.4 asks for on 7 point-to-point xGMI links), and reports
 nccl-tests style algorithm / bus bandwidth (busbw = algbw * (n-1)/n for RS / AG, 2(n-1)/n for
-AR) with the time taken as the MAX over ranks.  bench.py runs it after the timed region at
-world > 1 so the driver's multi-GPU runs carry a measured xGMI collective curve next to the
+AR) with the time taken as the MAX over ranks.  ``bench.py --full`` runs it after the timed region
+at world > 1 so the driver's multi-GPU runs carry a measured xGMI collective curve next to the
 throughput number (bucket size is chosen against this curve: 7 point-to-point
 links per GPU make ring collectives per-link bound, so small buckets sit on the latency floor).
 

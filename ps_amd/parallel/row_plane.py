@@ -87,7 +87,7 @@ class RowPlane:
         self._ev = None
         self._peer_ev = None
         self.stats = {"pulls": 0, "pushes": 0, "grows": 0, "host_syncs": 0}
-        # per-stage timing (bench --timing / PS_AMD_ROWPLANE_TIMING=1): device events around each
+        # per-stage timing (bench --full --timing / PS_AMD_ROWPLANE_TIMING=1): device events around each
         # stage's own work and host wall time in each cross-rank wait, plus the bytes every stage
         # moves (``timing_summary``)
         self.timing = os.environ.get("PS_AMD_ROWPLANE_TIMING", "0") == "1"
