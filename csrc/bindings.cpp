@@ -1323,8 +1323,8 @@ static std::pair<psamd::ConvGeo, int64_t> conv_geo(const Tensor& a, const std::v
   return {g, a.size(0) / (H * W)};
 }
 
-// The tile plan conv_gemm picks: [bm, bn, gm] (src2: 0 one row source, 1 the block-output
-// prologue, 2 the BN-backward prologue) -- tests and the fused ResNet path use it to see which
+// The tile plan conv_gemm picks: [bm, bn, gm] (src2: psamd::ConvSrc2 -- 0 one row source, 1 the
+// block-output prologue, 2 the BN-backward prologue) -- tests and the fused ResNet path use it to see which
 // kernel family a shape runs on (bm = bn = 256: conv_big.hip)
 std::vector<int64_t> conv_gemm_plan(int64_t M, int64_t N, int64_t C, std::vector<int64_t> geo, bool pro, int64_t epi,
                                     int64_t src2) {
@@ -1338,7 +1338,10 @@ std::vector<int64_t> conv_gemm_plan(int64_t M, int64_t N, int64_t C, std::vector
   return {pl.bm, pl.bn, pl.gm};
 }
 
-// c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> [c, BN partials [2, G, N] (epi 1/3)]
+static bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> [c, BN partials [slabs, G, N] (epi_writes_sums)]
+// epi: psamd::ConvEpi (module attribute EPI); the prologue follows from pro / a2 / bwd (psamd::ConvPro)
 std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10::optional<Tensor> pro, int64_t epi,
                               c10::optional<Tensor> aux, c10::optional<Tensor> kshift, c10::optional<Tensor> mc,
                               c10::optional<Tensor> mean, c10::optional<Tensor> invstd, c10::optional<Tensor> bits,
@@ -1353,96 +1356,80 @@ std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10:
   const int64_t N = b.size(0), K = b.size(1);
   TORCH_CHECK(K == static_cast<int64_t>(g.ks) * g.ks * g.C, "b must be [N, ks*ks*C]");
   TORCH_CHECK(N % 64 == 0 && N <= 8192, "N must be a multiple of 64, <= 8192");
-  TORCH_CHECK(epi >= 0 && epi <= 9, "epi in 0..9");
-  const int base = epi == 6 || epi == 9 ? 5 : epi == 7 ? 2 : epi == 8 ? 4 : static_cast<int>(epi);
-  const bool fold = epi >= 6;
+  TORCH_CHECK(psamd::epi_valid(epi), "epi in 0..9");
+  const int e = static_cast<int>(epi);
   const int64_t M = gi.second * g.OH * g.OW;
   TORCH_CHECK(M > 0 && M < (int64_t(1) << 31), "pixel count");
-  const uint16_t* auxp = nullptr;
-  if (epi >= 2) {
-    TORCH_CHECK(aux.has_value() && aux->defined(), "epi ", epi, " needs aux");
+  // the prologue: bwd -> BN backward (a, a2); pro + a2 -> block output; pro -> BN + ReLU
+  const bool has_pro = has(pro), has_bwd = has(bwd), resp = has(a2) && !has_bwd;
+  TORCH_CHECK(!has_bwd || !has_pro, "the BN-backward prologue excludes pro");
+  TORCH_CHECK(!resp || has_pro, "a2 without bwd is the block-output prologue: needs pro");
+  TORCH_CHECK(!has_bwd || has(a2), "the BN-backward prologue needs a2");
+  const int mode = has_bwd   ? psamd::kProBnBwd
+                   : resp    ? psamd::kProBlockOut
+                   : has_pro ? psamd::kProBnRelu
+                             : psamd::kProNone;
+  const int src2 = psamd::pro_src2(mode);
+  TORCH_CHECK(src2 == psamd::kSrc2None || (g.ks == 1 && g.stride == 1 && g.pad == 0),
+              "the two-source prologues are for 1x1 stride-1 convs");
+  TORCH_CHECK(psamd::conv_pro_epi_exists(mode, e), "no kernel pairs prologue ", mode, " with epilogue ", e,
+              ": pro / the block-output prologue take epilogue 0 or 1, the BN-backward prologue 2-9");
+  const auto pl = psamd::conv_fwd_plan_geo(static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
+                                           mode != psamd::kProNone, g, src2, e);
+  const bool big = pl.bm == 256 && pl.bn == 256;
+  TORCH_CHECK(psamd::conv_fwd_runs(pl, mode, e), "the ", pl.bm, " x ", pl.bn,
+              " tiles planned for this shape have no kernel for prologue ", mode, " with epilogue ", e);
+  if (psamd::epi_reads_aux(e)) {
+    TORCH_CHECK(has(aux), "epi ", epi, " needs aux");
     check_rows(*aux, "aux");
-    const int64_t want = base == 4 ? gi.second * ((g.OH + 1) / 2) * ((g.OW + 1) / 2) * N : M * N;
+    const int64_t want =
+        psamd::epi_base(e) == psamd::kEpiAddS2 ? gi.second * ((g.OH + 1) / 2) * ((g.OW + 1) / 2) * N : M * N;
     TORCH_CHECK(aux->numel() == want, "aux has ", aux->numel(), " elements, expected ", want);
-    auxp = u16(*aux);
   }
-  if (epi == 3) TORCH_CHECK(mc.has_value() && mean.has_value() && invstd.has_value(), "epi 3 needs mc, mean, invstd");
-  const uint8_t* bitsp = nullptr;
-  if (base == 5) {
-    TORCH_CHECK(bits.has_value() && bits->defined(), "epi 5/6 needs bits");
+  if (e == psamd::kEpiMaskSums)
+    TORCH_CHECK(mc.has_value() && mean.has_value() && invstd.has_value(), "epi ", epi, " needs mc, mean, invstd");
+  if (psamd::epi_needs_bits(e)) {
+    TORCH_CHECK(has(bits), "epi ", epi, " needs bits");
     check_gpu(*bits, "bits");
     TORCH_CHECK(bits->scalar_type() == torch::kUInt8 && bits->numel() * 8 == M * N, "bits: uint8 [M * N / 8]");
-    bitsp = bits->data_ptr<uint8_t>();
   }
-  TORCH_CHECK(!(pro.has_value() && pro->defined()) || epi <= 1, "the BN prologue combines with epilogue 0 or 1 only");
-  const bool has_bwd = bwd.has_value() && bwd->defined();
-  if (has_bwd) {  // BN-backward prologue: A := ca * a + cb * a2 + cc, stored to a third output
-    TORCH_CHECK(!(pro.has_value() && pro->defined()), "the BN-backward prologue excludes pro");
-    TORCH_CHECK(epi == 3 || ((epi == 2 || epi >= 4) &&
-                             psamd::conv_big_ok(static_cast<int>(gi.second * g.OH * g.OW), static_cast<int>(N),
-                                                static_cast<int>(K), true, g, 2, static_cast<int>(epi))),
-                "the BN-backward prologue combines with epi 3, or with 2 / 4-9 on the 256 x 256 tiles");
-    TORCH_CHECK(g.ks == 1 && g.stride == 1 && g.pad == 0, "the BN-backward prologue is for 1x1 stride-1 convs");
-    TORCH_CHECK(a2.has_value() && a2->defined(), "the BN-backward prologue needs a2");
+  if (psamd::epi_needs_aux2(e)) {
+    TORCH_CHECK(has(aux2) && has(bits2) && mean.has_value() && invstd.has_value(), "epi ", epi,
+                " needs aux2, bits2, mean, invstd");
+    check_rows(*aux2, "aux2");
+    TORCH_CHECK(aux2->numel() == M * N, "aux2 must be [M, N]");
+    check_gpu(*bits2, "bits2");
+    TORCH_CHECK(bits2->scalar_type() == torch::kUInt8 && bits2->numel() * 8 == M * N, "bits2: uint8 [M * N / 8]");
+  }
+  if (psamd::epi_needs_aux3(e)) {
+    TORCH_CHECK(has(aux3) && mean2.has_value() && invstd2.has_value(), "epi ", epi, " needs aux3, mean2, invstd2");
+    check_rows(*aux3, "aux3");
+    TORCH_CHECK(aux3->numel() == M * N, "aux3 must be [M, N]");
+  }
+  if (src2 != psamd::kSrc2None) {
     check_rows(*a2, "a2");
     TORCH_CHECK(a2->sizes() == a.sizes(), "a2 must match a");
+  }
+  if (has_bwd) {  // A := ca * a + cb * a2 + cc, stored to a third output
     check_f32(*bwd, "bwd");
     TORCH_CHECK(bwd->numel() == 3 * g.C, "bwd must be [3C]");
   }
-  // block-output prologue: A := relu(bn3(a) + r), r = a2 or the downsample BN of a2 (pro2); the
-  // block output and its ReLU bits land in the caller's aout / abits
-  const bool has_a2 = a2.has_value() && a2->defined();
-  const bool resp = has_a2 && !has_bwd;
-  if (resp) {
-    TORCH_CHECK(pro.has_value() && pro->defined(), "a2 without bwd is the block-output prologue: needs pro");
-    TORCH_CHECK(g.ks == 1 && g.stride == 1 && g.pad == 0, "the block-output prologue is for 1x1 stride-1 convs");
-    check_rows(*a2, "a2");
-    TORCH_CHECK(a2->sizes() == a.sizes(), "a2 must match a");
-    TORCH_CHECK(aout.has_value() && aout->defined() && abits.has_value() && abits->defined(),
-                "the block-output prologue needs aout and abits");
+  if (resp) {  // A := relu(bn3(a) + r), r = a2 or the downsample BN of a2 (pro2) -> the caller's aout / abits
+    TORCH_CHECK(has(aout) && has(abits), "the block-output prologue needs aout and abits");
     check_rows(*aout, "aout");
     TORCH_CHECK(aout->sizes() == a.sizes(), "aout must match a");
     check_gpu(*abits, "abits");
     TORCH_CHECK(abits->scalar_type() == torch::kUInt8 && abits->is_contiguous() && abits->numel() * 8 == a.numel(),
                 "abits: uint8 [rows * C / 8]");
   } else {
-    TORCH_CHECK(!(pro2.has_value() && pro2->defined()) && !(aout.has_value() && aout->defined()),
-                "pro2 / aout belong to the block-output prologue (pro + a2)");
-  }
-  const uint16_t* aux2p = nullptr;
-  const uint8_t* bits2p = nullptr;
-  if (fold) {
-    TORCH_CHECK(aux2.has_value() && aux2->defined() && bits2.has_value() && bits2->defined() && mean.has_value() &&
-                    invstd.has_value(),
-                "epi ", epi, " needs aux2, bits2, mean, invstd");
-    check_rows(*aux2, "aux2");
-    TORCH_CHECK(aux2->numel() == M * N, "aux2 must be [M, N]");
-    check_gpu(*bits2, "bits2");
-    TORCH_CHECK(bits2->scalar_type() == torch::kUInt8 && bits2->numel() * 8 == M * N, "bits2: uint8 [M * N / 8]");
-    aux2p = u16(*aux2);
-    bits2p = bits2->data_ptr<uint8_t>();
-  }
-  const uint16_t* aux3p = nullptr;
-  if (epi == 9) {
-    TORCH_CHECK(aux3.has_value() && aux3->defined() && mean2.has_value() && invstd2.has_value(),
-                "epi 9 needs aux3, mean2, invstd2");
-    check_rows(*aux3, "aux3");
-    TORCH_CHECK(aux3->numel() == M * N, "aux3 must be [M, N]");
-    aux3p = u16(*aux3);
+    TORCH_CHECK(!has(pro2) && !has(aout), "pro2 / aout belong to the block-output prologue (pro + a2)");
   }
   const c10::DeviceGuard guard(a.device());
   auto c = torch::empty({M, N}, a.options());
-  auto fopt = a.options().dtype(torch::kFloat32);
-  const bool has_pro = pro.has_value() && pro->defined();
-  const int G = psamd::conv_fwd_plan_geo(static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
-                                        has_pro || has_bwd, g, resp ? 1 : has_bwd ? 2 : 0, static_cast<int>(epi)).gm;
   b = b.contiguous();  // b may be a strided view (e.g. a transposed weight)
   check_rows(b, "b");
-  const bool sums = epi == 1 || epi == 3 || fold;
-  TORCH_CHECK(epi != 9 || psamd::conv_fwd_plan_geo(static_cast<int>(M), static_cast<int>(N), static_cast<int>(K),
-                                                   has_pro || has_bwd, g, 0, static_cast<int>(epi)).bm >= 128,
-              "epi 9 runs on the 128- or 256-pixel tiles");
-  Tensor part = sums ? torch::empty({epi == 9 ? 3 : 2, G, N}, fopt) : Tensor();
+  const bool sums = psamd::epi_writes_sums(e);
+  Tensor part = sums ? torch::empty({psamd::epi_sum_slabs(e), pl.gm, N}, a.options().dtype(torch::kFloat32)) : Tensor();
   psamd::ConvGemmArgs p{};
   p.a = u16(a);
   p.b = u16(b);
@@ -1452,19 +1439,19 @@ std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10:
   p.K = static_cast<int>(K);
   p.g = g;
   p.pro = f32_opt(pro, 2 * g.C, "pro");
-  p.epi = static_cast<int>(epi);
-  p.aux = auxp;
-  p.bits = bitsp;
-  p.aux2 = aux2p;
-  p.bits2 = bits2p;
+  p.epi = e;
+  p.aux = psamd::epi_reads_aux(e) ? u16(*aux) : nullptr;
+  p.bits = psamd::epi_needs_bits(e) ? bits->data_ptr<uint8_t>() : nullptr;
+  p.aux2 = psamd::epi_needs_aux2(e) ? u16(*aux2) : nullptr;
+  p.bits2 = psamd::epi_needs_aux2(e) ? bits2->data_ptr<uint8_t>() : nullptr;
   p.kshift = f32_opt(kshift, N, "kshift");
   p.mc = f32_opt(mc, 2 * N, "mc");
   p.mean = f32_opt(mean, N, "mean");
   p.invstd = f32_opt(invstd, N, "invstd");
   p.part = sums ? part.data_ptr<float>() : nullptr;
-  p.aux3 = aux3p;
-  p.mean2 = epi == 9 ? f32_opt(mean2, N, "mean2") : nullptr;
-  p.invstd2 = epi == 9 ? f32_opt(invstd2, N, "invstd2") : nullptr;
+  p.aux3 = psamd::epi_needs_aux3(e) ? u16(*aux3) : nullptr;
+  p.mean2 = psamd::epi_needs_aux3(e) ? f32_opt(mean2, N, "mean2") : nullptr;
+  p.invstd2 = psamd::epi_needs_aux3(e) ? f32_opt(invstd2, N, "invstd2") : nullptr;
   Tensor bwd_out;
   if (has_bwd) {
     bwd_out = torch::empty_like(a);
@@ -1478,30 +1465,36 @@ std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10:
     p.aout = u16m(*aout);
     p.abits = abits->data_ptr<uint8_t>();
   }
-  if (tbuf.has_value() && tbuf->defined()) {  // phase stamps of the 256 x 256-tile kernel (probes)
+  if (has(tbuf)) {  // phase stamps of the 256 x 256-tile kernel (probes)
     check_gpu(*tbuf, "tbuf");
     TORCH_CHECK(tbuf->scalar_type() == torch::kInt64 && tbuf->is_contiguous(), "tbuf: int64");
-    const auto pl = psamd::conv_fwd_plan_geo(p.M, p.N, p.K, has_pro || has_bwd, g, resp ? 1 : has_bwd ? 2 : 0, p.epi);
     TORCH_CHECK(pl.bm == 256 && tbuf->numel() >= int64_t(8) * pl.gm * (N / pl.bn), "tbuf: [8 x blocks] on the big tiles");
     p.tbuf = reinterpret_cast<uint64_t*>(tbuf->data_ptr<int64_t>());
   }
-  if (g_route_on.load(std::memory_order_relaxed)) {
-    const auto pl = psamd::conv_fwd_plan_geo(p.M, p.N, p.K, has_pro || has_bwd, g, resp ? 1 : has_bwd ? 2 : 0, p.epi);
-    route((pl.bm == 256 && pl.bn == 256 ? std::string("conv_big") : "conv_fwd_" + std::to_string(pl.bm) + "x" +
-                                                                          std::to_string(pl.bn)) +
-          "/k" + std::to_string(g.ks) + (g.stride == 2 ? "s2" : "") + (has_pro ? "/pro" : "") + (has_bwd ? "/bnbwd" : "") +
+  if (g_route_on.load(std::memory_order_relaxed))
+    route((big ? std::string("conv_big") : "conv_fwd_" + std::to_string(pl.bm) + "x" + std::to_string(pl.bn)) + "/k" +
+          std::to_string(g.ks) + (g.stride == 2 ? "s2" : "") + (has_pro ? "/pro" : "") + (has_bwd ? "/bnbwd" : "") +
           (resp ? "/blockout" : "") + "/epi" + std::to_string(epi));
-  }
   psamd::launch_conv_fwd(p, cur_stream(a));
   if (has_bwd) return {c, part, bwd_out};
   return {c, part};
+}
+
+// Whether conv_wgrad runs the 3x3 patch kernel for this layer (csrc convgemm.hip patch_ok):
+// geo = [H, W, OH, OW, ks, stride, pad], N output / C input channels
+bool conv_wgrad_patch_ok(std::vector<int64_t> geo, int64_t images, int64_t N, int64_t C) {
+  TORCH_CHECK(geo.size() == 7, "geo = [H, W, OH, OW, ks, stride, pad]");
+  const psamd::ConvGeo g{static_cast<int>(geo[0]), static_cast<int>(geo[1]), static_cast<int>(geo[2]),
+                         static_cast<int>(geo[3]), static_cast<int>(C), static_cast<int>(geo[4]),
+                         static_cast<int>(geo[5]), static_cast<int>(geo[6])};
+  return psamd::conv_wgrad_patch_ok(g, static_cast<int>(images * geo[2] * geo[3]), static_cast<int>(N), false);
 }
 
 // Data gradient of a 3x3 / stride-2 / pad-1 convolution as four stride-1 phase GEMMs over dz:
 // input pixel (2i + a, 2j + b) gathers dz rows i (+1) with the taps kh = 1 (a = 0) or kh = 2, 0
 // (a = 1) -- likewise for the width -- so phase (a, b) is a 1x1 / 1x2 / 2x1 / 2x2 "convolution"
 // over the dz map whose epilogue writes every other row of dx.  Every dx pixel is written by
-// exactly one phase (H, W even): no zero fill, no scatter-add.  epi 3 (z1, mc, mean, invstd):
+// exactly one phase (H, W even): no zero fill, no scatter-add.  kEpiMaskSums (z1, mc, mean, invstd):
 // ReLU mask of the BN that produced the conv input + its backward sums; partials of the four
 // phases are concatenated along the partial-row axis.
 //   dz [n*OH*OW, C2], wph: 4 weights [C1, nh*nw*C2] in phase order (0,0) (0,1) (1,0) (1,1)
@@ -1511,15 +1504,16 @@ std::vector<Tensor> conv_dgrad_s2(Tensor dz, std::vector<Tensor> wph, int64_t H,
   check_rows(dz, "dz");
   TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && H > 0 && W > 0, "stride-2 phases need an even input map");
   TORCH_CHECK(wph.size() == 4, "four phase weights");
-  TORCH_CHECK(epi == 0 || epi == 3, "epi 0 or 3");
+  TORCH_CHECK(psamd::conv_dgrad_phases_runs(static_cast<int>(epi)), "epi 0 or 3");
+  const bool sums = epi == psamd::kEpiMaskSums;
   const int64_t OH = H / 2, OW = W / 2, C2 = dz.size(1);
   TORCH_CHECK(C2 % 64 == 0 && dz.size(0) % (OH * OW) == 0, "dz must be [images*OH*OW, C2], C2 % 64 == 0");
   const int64_t imgs = dz.size(0) / (OH * OW), M = imgs * OH * OW, C1 = wph[0].size(0);
   TORCH_CHECK(C1 % 64 == 0 && C1 <= 8192 && imgs * H * W < (int64_t(1) << 31), "C1 / size");
   const uint16_t* zp = nullptr;
-  if (epi == 3) {
+  if (sums) {
     TORCH_CHECK(z.has_value() && z->defined() && mc.has_value() && mean.has_value() && invstd.has_value(),
-                "epi 3 needs z, mc, mean, invstd");
+                "epi ", epi, " needs z, mc, mean, invstd");
     check_rows(*z, "z");
     TORCH_CHECK(z->numel() == imgs * H * W * C1, "z must be [images*H*W, C1]");
     zp = u16(*z);
@@ -1532,7 +1526,7 @@ std::vector<Tensor> conv_dgrad_s2(Tensor dz, std::vector<Tensor> wph, int64_t H,
     ws.reserve(4);
     psamd::ConvGemmArgs ps[4] = {};
     const int gm = psamd::conv_dgrad_phase_gm(static_cast<int>(M));
-    Tensor part = epi == 3 ? torch::empty({2, 4 * gm, C1}, dz.options().dtype(torch::kFloat32)) : Tensor();
+    Tensor part = sums ? torch::empty({2, 4 * gm, C1}, dz.options().dtype(torch::kFloat32)) : Tensor();
     for (int ph = 0; ph < 4; ++ph) {
       const int a = ph >> 1, b = ph & 1, nh = a ? 2 : 1, nw = b ? 2 : 1;
       ws.push_back(wph[ph].contiguous());
@@ -1549,7 +1543,7 @@ std::vector<Tensor> conv_dgrad_s2(Tensor dz, std::vector<Tensor> wph, int64_t H,
       p.g = psamd::ConvGeo{static_cast<int>(OH), static_cast<int>(OW), static_cast<int>(OH), static_cast<int>(OW),
                            static_cast<int>(C2), nh, 1, 0, nw, static_cast<int>(H), static_cast<int>(W), a, b};
       p.epi = static_cast<int>(epi);
-      if (epi == 3) {
+      if (sums) {
         p.aux = zp;
         p.mc = f32_opt(mc, 2 * C1, "mc");
         p.mean = f32_opt(mean, C1, "mean");
@@ -1598,7 +1592,7 @@ Tensor conv_wgrad(Tensor dz, Tensor x, std::vector<int64_t> geo, c10::optional<T
 
 // conv3's backward in one pass (csrc/kernels/conv_bwd_fused.hip): bn3's backward prologue
 // dz3 = bf16(ca g + cb z3 + cc) never leaves LDS; -> [gy [M, CI] (masked by bn2's ReLU), part
-// [2, G, CI] (bn2 backward sums, the conv_gemm epi-3 layout), dW3 [CO, CI] bf16]
+// [2, G, CI] (bn2 backward sums, the conv_gemm kEpiMaskSums layout), dW3 [CO, CI] bf16]
 std::vector<Tensor> conv11_bwd_fused(Tensor g, Tensor z3, Tensor cbwd, Tensor wt, Tensor z2, c10::optional<Tensor> cf2,
                                      c10::optional<Tensor> mean2, c10::optional<Tensor> invstd2) {
   check_rows(g, "g");
@@ -1748,7 +1742,7 @@ std::vector<Tensor> bn_bwd_coef(Tensor part, c10::optional<Tensor> gamma, Tensor
   return {dg, db, coef};
 }
 
-// BN backward from producer partial sums part [2, G, C] (conv_gemm epi 3); g = masked gradient
+// BN backward from producer partial sums part [2, G, C] (conv_gemm kEpiMaskSums); g = masked gradient
 std::vector<Tensor> bn_bwd_partials(Tensor g, Tensor x, Tensor part, c10::optional<Tensor> gamma, Tensor mean,
                                     Tensor invstd) {
   check_rows(g, "g");
@@ -1796,6 +1790,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("epi") = 0, py::arg("z") = py::none(), py::arg("mc") = py::none(), py::arg("mean") = py::none(),
         py::arg("invstd") = py::none());
   m.def("conv_wgrad", &conv_wgrad, py::arg("dz"), py::arg("x"), py::arg("geo"), py::arg("pro") = py::none());
+  m.def("conv_wgrad_patch_ok", &conv_wgrad_patch_ok, py::arg("geo"), py::arg("images"), py::arg("N"), py::arg("C"));
+  {  // psamd::ConvEpi for ps_amd/ops/convgemm.py Epi
+    py::dict epi;
+    epi["STORE"] = static_cast<int>(psamd::kEpiStore);
+    epi["STATS"] = static_cast<int>(psamd::kEpiStats);
+    epi["ADD"] = static_cast<int>(psamd::kEpiAdd);
+    epi["MASK_SUMS"] = static_cast<int>(psamd::kEpiMaskSums);
+    epi["ADD_S2"] = static_cast<int>(psamd::kEpiAddS2);
+    epi["ADD_MASKED"] = static_cast<int>(psamd::kEpiAddMasked);
+    epi["FOLD_ADD_MASKED"] = static_cast<int>(psamd::kEpiFoldAddMasked);
+    epi["FOLD_ADD"] = static_cast<int>(psamd::kEpiFoldAdd);
+    epi["FOLD_ADD_S2"] = static_cast<int>(psamd::kEpiFoldAddS2);
+    epi["FOLD_ADD_MASKED_DS"] = static_cast<int>(psamd::kEpiFoldAddMaskedDs);
+    m.attr("EPI") = epi;
+  }
+  m.attr("kTwosrcGldsMinNk") = psamd::kTwosrcGldsMinNk;
   m.def("conv_gemm_plan", &conv_gemm_plan, py::arg("M"), py::arg("N"), py::arg("C"), py::arg("geo"),
         py::arg("pro") = false, py::arg("epi") = 0, py::arg("src2") = 0);
   m.def("conv11_bwd_fused", &conv11_bwd_fused, py::arg("g"), py::arg("z3"), py::arg("cbwd"), py::arg("wt"), py::arg("z2"),

@@ -7,6 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdexcept>
+#include <string>
+
 namespace psamd {
 
 // ---------------------------------------------------------------- optim.hip
@@ -318,6 +321,88 @@ inline FastDiv make_fastdiv(uint32_t d) {
   const uint64_t one = 1;
   return FastDiv{static_cast<uint32_t>(((one << 32) * ((one << sh) - d)) / d + 1), sh};
 }
+// conv_gemm's contract: which epilogue runs on the output tile, which prologue on the A rows.
+// The values are the binding's ``epi`` integers and the kernels' EPI / PRO template arguments.
+enum ConvEpi : int {
+  kEpiStore = 0,            // c = the GEMM result
+  kEpiStats = 1,            // + BN partial sums of c about kshift -> part
+  kEpiAdd = 2,              // + residual rows aux
+  kEpiMaskSums = 3,         // ReLU mask of the BN (mc, input z = aux) + its backward sums (mean, invstd) -> part
+  kEpiAddS2 = 4,            // + residual aux of the (OH+1)/2 x (OW+1)/2 map at even (h, w)
+  kEpiAddMasked = 5,        // + aux * relu'(forward output), the mask from bits
+  // the fold epilogues: a base epilogue + the previous block's bn3 backward reduce (aux2, bits2,
+  // mean, invstd) -- the output is masked by bits2 and its sums go to part
+  kEpiFoldAddMasked = 6,    // kEpiAddMasked + fold
+  kEpiFoldAdd = 7,          // kEpiAdd + fold
+  kEpiFoldAddS2 = 8,        // kEpiAddS2 + fold
+  kEpiFoldAddMaskedDs = 9,  // kEpiFoldAddMasked + the previous block's downsample-BN sum (aux3, mean2,
+                            // invstd2) as a third slab of part
+  kEpiCount = 10
+};
+enum ConvPro : int {
+  kProNone = 0,
+  kProBnRelu = 1,    // A := relu(A * scale + shift) while staging (pro)
+  kProBnBwd = 2,     // A := bf16(ca * a + cb * a2 + cc), also stored to aout (bwd, a2)
+  kProBlockOut = 3   // A := relu(a * sc + sh + r), r = a2 or a2 * sc2 + sh2; -> aout, abits (pro, a2, pro2)
+};
+// the launch's two-source prologue, as the tile plans see it
+enum ConvSrc2 : int { kSrc2None = 0, kSrc2BlockOut = 1, kSrc2BnBwd = 2 };
+
+// The one decode of an epilogue number.
+constexpr bool epi_valid(int64_t e) { return e >= kEpiStore && e < kEpiCount; }
+constexpr bool epi_folds_ds(int e) { return e == kEpiFoldAddMaskedDs; }
+constexpr bool epi_folds(int e) {
+  return e == kEpiFoldAddMasked || e == kEpiFoldAdd || e == kEpiFoldAddS2 || epi_folds_ds(e);
+}
+constexpr int epi_base(int e) {  // the epilogue a fold epilogue extends (itself for the others)
+  return e == kEpiFoldAddMasked || epi_folds_ds(e) ? kEpiAddMasked
+         : e == kEpiFoldAdd                        ? kEpiAdd
+         : e == kEpiFoldAddS2                      ? kEpiAddS2
+                                                   : e;
+}
+constexpr bool epi_writes_sums(int e) { return e == kEpiStats || e == kEpiMaskSums || epi_folds(e); }
+constexpr int epi_sum_slabs(int e) { return epi_folds_ds(e) ? 3 : 2; }  // part is [slabs][gm][N]
+constexpr bool epi_reads_aux(int e) { return e != kEpiStore && e != kEpiStats; }
+constexpr bool epi_needs_bits(int e) { return epi_base(e) == kEpiAddMasked; }
+constexpr bool epi_needs_aux2(int e) { return epi_folds(e); }  // aux2, bits2, mean, invstd
+constexpr bool epi_needs_aux3(int e) { return epi_folds_ds(e); }  // aux3, mean2, invstd2
+constexpr bool epi_is_fwd(int e) { return e == kEpiStore || e == kEpiStats; }
+// Whether any kernel pairs this prologue with this epilogue: the forward prologues feed the
+// forward epilogues, the BN-backward prologue a data-gradient epilogue (the 128-pixel tiles only
+// kEpiMaskSums: conv_fwd_runs).
+constexpr bool conv_pro_epi_exists(int pro, int epi) {
+  return epi_valid(epi) && (pro == kProNone || ((pro == kProBnRelu || pro == kProBlockOut) && epi_is_fwd(epi)) ||
+                            (pro == kProBnBwd && !epi_is_fwd(epi)));
+}
+constexpr int pro_src2(int pro) {
+  return pro == kProBlockOut ? kSrc2BlockOut : pro == kProBnBwd ? kSrc2BnBwd : kSrc2None;
+}
+// Launch ladders.  `switch (epi) { PSAMD_EPIS_X(L, args) default: conv_no_kernel(pro, epi); }`
+// runs L(args, E) for the epilogues E that set X lists and throws for every other: the lists are
+// the kernel instantiations of the launchers.  (kEpiStore comes last in each: the order the
+// kernels have had in the code object.)
+#define PSAMD_EPI_CASE(L, E, ...) \
+  case E: L(__VA_ARGS__, E); break;
+#define PSAMD_EPIS_FWD(L, ...) PSAMD_EPI_CASE(L, kEpiStats, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
+#define PSAMD_EPIS_ADD(L, ...) /* the residual / fold epilogues every tile has */                                  \
+  PSAMD_EPI_CASE(L, kEpiAddS2, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiAddMasked, __VA_ARGS__)                          \
+  PSAMD_EPI_CASE(L, kEpiFoldAddMasked, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiFoldAdd, __VA_ARGS__)                    \
+  PSAMD_EPI_CASE(L, kEpiFoldAddS2, __VA_ARGS__)
+#define PSAMD_EPIS_NO_DS(L, ...) /* all but kEpiFoldAddMaskedDs */                                                 \
+  PSAMD_EPI_CASE(L, kEpiStats, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiAdd, __VA_ARGS__)                                \
+  PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__) PSAMD_EPIS_ADD(L, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
+#define PSAMD_EPIS_ALL(L, ...)                                                                                     \
+  PSAMD_EPI_CASE(L, kEpiStats, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiAdd, __VA_ARGS__)                                \
+  PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__) PSAMD_EPIS_ADD(L, __VA_ARGS__)                                      \
+  PSAMD_EPI_CASE(L, kEpiFoldAddMaskedDs, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
+#define PSAMD_EPIS_DGRAD(L, ...) /* all but the forward ones (the BN-backward prologue on the 256 x 256 tiles) */  \
+  PSAMD_EPI_CASE(L, kEpiAdd, __VA_ARGS__) PSAMD_EPIS_ADD(L, __VA_ARGS__)                                           \
+  PSAMD_EPI_CASE(L, kEpiFoldAddMaskedDs, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__)
+[[noreturn]] inline void conv_no_kernel(int pro, int epi) {
+  throw std::invalid_argument("conv_gemm: no kernel for prologue " + std::to_string(pro) + " with epilogue " +
+                              std::to_string(epi) + " on this tile");
+}
+
 struct ConvGemmArgs {
   const uint16_t* a;    // [images, H, W, C] bf16
   const uint16_t* b;    // [N, K] bf16, K = ks * ks * C
@@ -325,59 +410,68 @@ struct ConvGemmArgs {
   int M, N, K;
   ConvGeo g;
   const float* pro;     // [scale | shift] (2C): A := relu(A * scale + shift) while staging; nullable
-  int epi;              // 0 store, 1 + BN partial sums, 2 + residual, 3 ReLU mask + BN-backward sums,
-                        // 4 + residual of the (OH+1)/2 x (OW+1)/2 map at even (h, w),
-                        // 5 + residual masked by bits (aux * relu'(forward output)),
-                        // 6/7/8 = 5/2/4 + the previous block's bn3 backward reduce (aux2, bits2,
-                        // mean, invstd): output masked by bits2, sums into part; 9 = 6 + the
-                        // previous block's downsample-BN sum (aux3, mean2, invstd2)
-  const uint16_t* aux;  // epi 2/4/5: residual rows; epi 3: BN input z [M, N]
-  const uint8_t* bits;  // epi 5/6: ReLU mask bits of aux's elements
-  const uint16_t* aux2; // epi 6-8: previous block's bn3 input z3 [M, N]
-  const uint8_t* bits2; // epi 6-8: ReLU mask bits of the previous block's output (= this input)
-  const float* kshift;  // epi 1: shift of the partial sums [N] (nullable = 0)
-  const float* mc;      // epi 3: [scale | shift] (2N) of that BN (ReLU mask)
-  const float* mean;    // epi 3/6-8: [N]
-  const float* invstd;  // epi 3/6-8: [N]
-  float* part;          // epi 1/3/6-8: [2][conv_fwd_plan(M, N, K, pro).gm][N] block partial sums
-                        // (epi 9: [3][gm][N], the third = the downsample BN's sum(g * xhat))
-  const uint16_t* aux3; // epi 9: the previous block's downsample-BN input zd [M, N]
-  const float* mean2;   // epi 9: [N] that BN's batch mean / inverse std
+  int epi;              // ConvEpi
+  const uint16_t* aux;  // epi_reads_aux: residual rows; kEpiMaskSums: BN input z [M, N]
+  const uint8_t* bits;  // epi_needs_bits: ReLU mask bits of aux's elements
+  const uint16_t* aux2; // epi_needs_aux2: previous block's bn3 input z3 [M, N]
+  const uint8_t* bits2; // epi_needs_aux2: ReLU mask bits of the previous block's output (= this input)
+  const float* kshift;  // kEpiStats: shift of the partial sums [N] (nullable = 0)
+  const float* mc;      // kEpiMaskSums: [scale | shift] (2N) of that BN (ReLU mask)
+  const float* mean;    // kEpiMaskSums / epi_needs_aux2: [N]
+  const float* invstd;  // kEpiMaskSums / epi_needs_aux2: [N]
+  float* part;          // epi_writes_sums: [epi_sum_slabs][conv_fwd_plan(M, N, K, pro).gm][N] block partial sums
+  const uint16_t* aux3; // epi_needs_aux3: the previous block's downsample-BN input zd [M, N]
+  const float* mean2;   // epi_needs_aux3: [N] that BN's batch mean / inverse std
   const float* invstd2;
-  // BN-backward prologue (1x1, epi 3 only; excludes pro): A := bf16(ca * a + cb * a2 + cc), the
-  // previous BN's data gradient from its output gradient a and input a2 (coefficients bwd =
-  // [ca | cb | cc], 3C); the A tile is also stored to aout [M, C] (by the channel-tile-0 blocks)
+  // kProBnBwd (1x1; excludes pro): the previous BN's data gradient from its output gradient a and
+  // input a2 (coefficients bwd = [ca | cb | cc], 3C); the A tile is also stored to aout [M, C] (by
+  // the channel-tile-0 blocks)
   const uint16_t* a2;   // [M, C] BN input; nullable
   const float* bwd;     // [3C]
   uint16_t* aout;       // [M, C]
-  // block-output prologue (1x1 forward, epi 0/1; pro and a2 set, bwd null): A := relu(a * sc + sh
-  // + r) with pro = [sc | sh] of bn3 and r = a2 (identity) or a2 * sc2 + sh2 (pro2 = the
-  // downsample BN's [sc2 | sh2]); the block output goes to aout, its ReLU bits to abits [M C / 8]
+  // kProBlockOut (1x1 forward; pro and a2 set, bwd null): pro = [sc | sh] of bn3, r = a2 (identity)
+  // or a2 * sc2 + sh2 (pro2 = the downsample BN's [sc2 | sh2]); the block output goes to aout, its
+  // ReLU bits to abits [M C / 8]
   const float* pro2;    // [2C]; nullable
   uint8_t* abits;
   FastDiv fd_ohw, fd_ow;  // set by launch_conv_fwd (OH * OW, OW)
   int pgm;                // rows per partial slab (0: the launch's gm); several GEMMs share one part
   uint64_t* tbuf = nullptr;  // conv_big only, diagnostics: 8 wall-clock stamps per block (nullable)
 };
+// the prologue a launch runs, from the pointers that are set (the binding checks the rest)
+inline int conv_pro(const ConvGemmArgs& a) {
+  return a.bwd != nullptr ? kProBnBwd : a.pro == nullptr ? kProNone : a.a2 != nullptr ? kProBlockOut : kProBnRelu;
+}
+inline int conv_src2(const ConvGemmArgs& a) { return pro_src2(conv_pro(a)); }
 struct ConvFwdPlan {
   int bm, bn, gm;       // tile pixels / channels, pixel-tile groups (partial-sum rows)
 };
 ConvFwdPlan conv_fwd_plan(int M, int N, int K, bool pro, int epi = 0);
 // conv_big.hip: 256 x 256 tiles, one 512-thread block per CU, for deep-K 1x1 GEMMs (every epilogue);
-// conv_fwd_plan_geo / launch_conv_fwd route there when conv_big_ok holds (gm = conv_big_gm(M))
-bool conv_big_ok(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int epi);
-// the channel tile conv_big runs for this GEMM: 256, 128 (two blocks per CU), 0 = not eligible
+// conv_fwd_plan_geo / launch_conv_fwd route there when conv_big_tn is not 0 (gm = conv_big_gm(M))
+// the channel tile conv_big runs for this GEMM: 256, 0 = not eligible
 int conv_big_tn(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int epi);
 int conv_big_gm(int M);
+// whether launch_conv_big instantiates this (ConvPro, ConvEpi)
+bool conv_big_runs(int pro, int epi);
 void launch_conv_big(const ConvGemmArgs& a, hipStream_t s);
-// the four stride-2 data-gradient phase GEMMs (epi 3, no prologue, LDS-DMA staging, 128-pixel tiles)
-// in one launch; phase i's partials go to rows [sum gm(<i), ..) of a part with pgm = sum of gm
+// the four stride-2 data-gradient phase GEMMs (no prologue, LDS-DMA staging, 128-pixel tiles) in
+// one launch; phase i's partials go to rows [sum gm(<i), ..) of a part with pgm = sum of gm
 void launch_conv_dgrad_phases(const ConvGemmArgs* ph, hipStream_t s);
+bool conv_dgrad_phases_runs(int epi);  // kEpiStore or kEpiMaskSums
 int conv_dgrad_phase_gm(int M);
 // the plan launch_conv_fwd uses for this geometry (the 3x3 patch-staged tiles where they apply)
-// src2: the launch's two-source prologue (0 none, 1 block output, 2 BN backward)
+// src2: the launch's two-source prologue (ConvSrc2)
 ConvFwdPlan conv_fwd_plan_geo(int M, int N, int K, bool pro, const ConvGeo& g, int src2 = 0, int epi = 0);
+// whether the tile family of plan pl instantiates this (ConvPro, ConvEpi): launch_conv_fwd throws
+// std::invalid_argument where it does not, and the binding checks before it launches
+bool conv_fwd_runs(const ConvFwdPlan& pl, int pro, int epi);
 void launch_conv_fwd(const ConvGemmArgs& a, hipStream_t s);
+// two-source prologues with K >= 64 x this run on the LDS-DMA variant (convgemm.hip;
+// profiles/r4_twosrc_probe.txt: LDS-DMA ahead at every K >= 256)
+constexpr int kTwosrcGldsMinNk = 4;
+// whether launch_conv_wgrad runs the 3x3 patch kernel for this weight gradient (convgemm.hip)
+bool conv_wgrad_patch_ok(const ConvGeo& g, int M, int N, bool pro);
 // Backward layouts of many conv weights in one launch: jobs = device array of
 // {src, dst, kind (0 1x1 transpose, 1 3x3 flip-transpose, 2 3x3 stride-2 phases), A, B} (32 B each)
 void launch_weight_prep(const void* jobs, int njobs, int max_blocks, hipStream_t s);
@@ -385,7 +479,7 @@ void launch_weight_prep(const void* jobs, int njobs, int max_blocks, hipStream_t
 // Fused backward of a bottleneck's last 1x1 conv (conv3: CI -> CO channels) with bn3's backward
 // in its prologue (conv_bwd_fused.hip): per 128-pixel tile, dz3 = bf16(ca g + cb z3 + cc) is built
 // in LDS one 64-channel stage at a time and feeds BOTH GEMMs -- the data gradient
-// gy = dz3 W3 (bn2's ReLU mask + backward sums in the epilogue, the conv_gemm epi-3 contract) and
+// gy = dz3 W3 (bn2's ReLU mask + backward sums in the epilogue, the conv_gemm kEpiMaskSums contract) and
 // the weight gradient dW3 += dz3^T relu(bn2(z2)) (per-block fp32 slabs, fixed-order reduce) --
 // so dz3 never reaches HBM and z2 is read once for both.
 struct Conv11BwdArgs {

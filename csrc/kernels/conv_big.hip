@@ -14,8 +14,8 @@
 //     flight across the barrier (raw s_barrier: __syncthreads() would drain them);
 //   * fragment reads as inline asm, the next k-step's issued before this one's MFMAs;
 //   * the epilogue (plain store, BN statistics, the data-gradient ReLU mask + BN-backward sums,
-//     or the conv1 data gradients' residual / fold epilogues -- every conv_gemm epilogue 0-9) from
-//     a bf16 output tile in LDS, one 16-B column group per thread, rows coalesced.
+//     or the conv1 data gradients' residual / fold epilogues -- every conv_gemm epilogue, ConvEpi)
+//     from a bf16 output tile in LDS, one 16-B column group per thread, rows coalesced.
 // Blocks are XCD-remapped so the channel tiles of one pixel tile share its A rows in one L2.
 // What bounds it (profiles/r5_conv_big_kloop.txt): the K loop runs at the memory system's stage
 // rate (~64 KiB per 1.8 us per CU).  Variants measured and removed (round 6): 256 x 128 tiles two
@@ -89,9 +89,9 @@ __device__ __forceinline__ uint32_t fdiv_big(uint32_t n, const FastDiv& f) { ret
 __device__ __forceinline__ int bswz(int r, int c) { return c ^ ((r >> 1) & 7); }
 
 // PRO (conv_gemm's A prologues, applied by ONE in-place pass over each landed A stage):
-//   0 none; 1 relu(bf16(a sc + sh)) (the previous BN + ReLU); 2 the BN backward
+//   kProNone; kProBnRelu relu(bf16(a sc + sh)) (the previous BN + ReLU); kProBnBwd the BN backward
 //   bf16(ca a + cb a2 + cc) from two row sources, the result also stored to aout (the weight
-//   gradient's operand) by the channel-tile-0 blocks; 3 the previous block's output
+//   gradient's operand) by the channel-tile-0 blocks; kProBlockOut the previous block's output
 //   relu(a sc + sh + r), r = a2 or a2 sc2 + sh2, stored to aout with its ReLU bits (abits).
 // The second row source a2 lands by LDS-DMA into one extra 32 KiB tile, refilled for stage kt + 1
 // once the pass over stage kt has read it.  With a 256-wide channel tile the A rows are staged
@@ -99,15 +99,14 @@ __device__ __forceinline__ int bswz(int r, int c) { return c ^ ((r >> 1) & 7); }
 // channel tiles of the pixel tile run on the same XCD (L2 re-reads, not HBM).
 template <int EPI, int PRO>
 __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) {
-  static_assert(EPI >= 0 && EPI <= 9, "conv_gemm's epilogues");
-  static_assert(PRO != 2 || (EPI != 0 && EPI != 1), "the BN-backward prologue feeds a data-gradient GEMM");
+  static_assert(conv_pro_epi_exists(PRO, EPI), "conv_gemm's (prologue, epilogue) pairs");
 
   constexpr int BK = 64, TN = 256, NW = 8, NT = 64 * NW;
   constexpr int WCH = 64;                         // channels per wave (2 waves along the pixels)
   constexpr int WN = TN / WCH, TI = WCH / 32;     // waves along the channels; 32-ch blocks per wave
   constexpr int kRing = 131072;
   constexpr int kTN = TN, kCS = TN + 4;          // output tile row stride (elements)
-  constexpr bool TWO = PRO == 2 || PRO == 3;
+  constexpr bool TWO = pro_src2(PRO) != kSrc2None;
   constexpr int RB = 2 * BK;                    // bytes per stage row
   constexpr int A_BYTES = kTM * RB, STAGE = (kTM + kTN) * RB;
   constexpr int NST = kRing / STAGE;            // 2
@@ -183,19 +182,19 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
   // channels: one coefficient load per stage) of rows (t >> 3) + (NT / 8) i
   // coefficients of the pass over stage kt (thread t: logical chunk t & 7): NCO untracked 16-B loads
   // issued before the stage's DMA, waited for by vmcnt(GPS) behind it
-  constexpr int NCO = PRO == 1 ? 4 : PRO == 2 ? 6 : 8;
+  constexpr int NCO = PRO == kProBnRelu ? 4 : PRO == kProBnBwd ? 6 : 8;
   f32x4 co[NCO];
   auto load_coef = [&](int kt) {
     const int cc = kt * BK + (t & 7) * 8;
     const float* src[4] = {p.pro, p.pro, p.pro, p.pro};
-    if constexpr (PRO == 2) {
+    if constexpr (PRO == kProBnBwd) {
       src[0] = p.bwd;
       src[1] = p.bwd + g.C;
       src[2] = p.bwd + 2 * g.C;
     } else {
       src[0] = p.pro;
       src[1] = p.pro + g.C;
-      if constexpr (PRO == 3) {
+      if constexpr (PRO == kProBlockOut) {
         const bool dual = p.pro2 != nullptr;  // block-uniform; without it two dummy loads keep the count
         src[2] = dual ? p.pro2 : p.pro;
         src[3] = dual ? p.pro2 + g.C : p.pro;
@@ -231,8 +230,8 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
         c3[j + 4] = co[7][j];
       }
     }
-    const bool dual = PRO == 3 && p.pro2 != nullptr;
-    const bool store_a = (PRO == 2 || PRO == 3) && p.aout != nullptr && n0 == 0;
+    const bool dual = PRO == kProBlockOut && p.pro2 != nullptr;
+    const bool store_a = TWO && p.aout != nullptr && n0 == 0;
     constexpr int TRP = NT / 8, NR = kTM / TRP, HB = TWO ? 2 : NR;  // rows read together (register budget)
 #pragma unroll
     for (int h = 0; h < NR; h += HB) {
@@ -249,18 +248,18 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
       const int off = r * RB + bswz(r, lc) * 16;
       u16x8 v = va[i];
       unsigned ob = 0;
-      if constexpr (PRO == 1) {
+      if constexpr (PRO == kProBnRelu) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float o = bf16_to_f32(v[j]) * c0[j] + c1[j];
           v[j] = f32_to_bf16(o > 0.f ? o : 0.f);
         }
-      } else if constexpr (PRO == 2) {
+      } else if constexpr (PRO == kProBnBwd) {
         const u16x8 z8 = za[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           v[j] = f32_to_bf16(c0[j] * bf16_to_f32(v[j]) + c1[j] * bf16_to_f32(z8[j]) + c2[j]);
-      } else if constexpr (PRO == 3) {  // the arithmetic of bn_apply_kernel / bn_apply_dual_kernel
+      } else if constexpr (PRO == kProBlockOut) {  // the arithmetic of bn_apply_kernel / bn_apply_dual_kernel
         const u16x8 z8 = za[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
       if (store_a && ok) {
         const int64_t e = static_cast<int64_t>(m) * g.C + cc;
         *reinterpret_cast<u16x8*>(p.aout + e) = v;
-        if constexpr (PRO == 3) p.abits[e >> 3] = static_cast<uint8_t>(ob);
+        if constexpr (PRO == kProBlockOut) p.abits[e >> 3] = static_cast<uint8_t>(ob);
       }
     }
     }
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
     __builtin_amdgcn_s_setprio(0);
   };
 
-  if constexpr (PRO != 0) {
+  if constexpr (PRO != kProNone) {
     // stage kt + 1 (and a2 of kt + 1 once the pass over kt has read the a2 tile) in flight behind
     // stage kt's pass and MFMAs; the pass's aout stores drain with them
     issue(kb, 0);
@@ -379,9 +378,9 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
   // ---- prologue: stages 0 .. NST - 2 in flight
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s) {
-    if (PRO == 0 && kb + s < ke) issue(kb + s, s);
+    if (PRO == kProNone && kb + s < ke) issue(kb + s, s);
   }
-  for (int kt = kb; kt < (PRO == 0 ? ke : kb); ++kt) {
+  for (int kt = kb; kt < (PRO == kProNone ? ke : kb); ++kt) {
     // stage kt landed (this wave's DMAs): younger are the min(NST - 2, ke - 1 - kt) stages after it
     const int younger = min(NST - 2, ke - 1 - kt);
     if (younger >= 2) {
@@ -429,15 +428,12 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
   stamp(3);
 
   // ---- row pass: thread t owns channels [8 cg, 8 cg + 8) of rows r0 + 16 i
-  // EPI 5/6/9: + the residual rows masked by the block output's ReLU bits (aux, bits); EPI 2/7:
-  // + the residual rows; EPI 4/8: + the stride-2 residual map at even (h, w); 6-9 also mask by the
-  // previous block's output bits (bits2) and reduce its bn3 backward sums over aux2 (and, 9, the
-  // downsample BN's sum over aux3) -- conv_gemm's epilogues, see convgemm.hip conv_fwd_body
-  constexpr bool FOLD = EPI >= 6;
-  constexpr bool FOLD_DS = EPI == 9;
-  constexpr int BASE = EPI == 6 || EPI == 9 ? 5 : EPI == 7 ? 2 : EPI == 8 ? 4 : EPI;
-  constexpr bool SUMS = EPI == 1 || EPI == 3 || FOLD;
-  constexpr bool RD_AUX = BASE == 2 || BASE == 4 || BASE == 5 || EPI == 3;
+  // conv_gemm's epilogues (psamd_launch.h ConvEpi; the same row pass as convgemm.hip conv_fwd_body)
+  constexpr bool FOLD = epi_folds(EPI);
+  constexpr bool FOLD_DS = epi_folds_ds(EPI);
+  constexpr int BASE = epi_base(EPI);
+  constexpr bool SUMS = epi_writes_sums(EPI);
+  constexpr bool RD_AUX = epi_reads_aux(EPI);
   constexpr int CG = kTN / 8, RPP = NT / CG;  // 16-B column groups per row; rows per pass
   const int cg = t % CG, r0 = t / CG, nc = n0 + cg * 8;
   float e0[8], e1[8], e2[8], e3[8], s1[8], s2[8], s3[FOLD_DS ? 8 : 1], e4[FOLD_DS ? 8 : 1], e5[FOLD_DS ? 8 : 1];
@@ -449,9 +445,9 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
     load8(p.mean2, nc, e4);
     load8(p.invstd2, nc, e5);
   }
-  if constexpr (EPI == 1) {
+  if constexpr (EPI == kEpiStats) {
     if (p.kshift) load8(p.kshift, nc, e0);
-  } else if constexpr (EPI == 3) {
+  } else if constexpr (EPI == kEpiMaskSums) {
     load8(p.mc, nc, e0);
     load8(p.mc + p.N, nc, e1);
     load8(p.mean, nc, e2);
@@ -467,13 +463,13 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
 #pragma unroll
   for (int h = 0; h < NPASS; h += RIF) {
     u16x8 ra[RD_AUX ? RIF : 1], rz[FOLD ? RIF : 1], rd[FOLD_DS ? RIF : 1];
-    uint32_t rb[BASE == 5 ? RIF : 1], rp[FOLD ? RIF : 1];
+    uint32_t rb[epi_needs_bits(EPI) ? RIF : 1], rp[FOLD ? RIF : 1];
     unsigned rodd = 0;
 #pragma unroll
     for (int i = 0; i < RIF; ++i) {
       const int m = min(m0 + r0 + RPP * (h + i), p.M - 1);
       const int64_t o = static_cast<int64_t>(m) * p.N + nc;
-      if constexpr (BASE == 4) {  // residual map (OH+1)/2 x (OW+1)/2, present at even (h, w)
+      if constexpr (BASE == kEpiAddS2) {  // residual map (OH+1)/2 x (OW+1)/2, present at even (h, w)
         const int ohw = g.OH * g.OW;
         const int im = static_cast<int>(fdiv_big(static_cast<uint32_t>(m), p.fd_ohw)), r = m - im * ohw,
                   hh = static_cast<int>(fdiv_big(static_cast<uint32_t>(r), p.fd_ow)), ww = r - hh * g.OW;
@@ -484,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
       } else if constexpr (RD_AUX) {
         ra[i] = *reinterpret_cast<const u16x8*>(p.aux + o);
       }
-      if constexpr (BASE == 5) rb[i] = p.bits[o >> 3];
+      if constexpr (BASE == kEpiAddMasked) rb[i] = p.bits[o >> 3];
       if constexpr (FOLD) {
         rz[i] = *reinterpret_cast<const u16x8*>(p.aux2 + o);
         rp[i] = p.bits2[o >> 3];
@@ -498,21 +494,21 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
       const u16x4 lo = *reinterpret_cast<const u16x4*>(Cs + rr * kCS + cg * 8);
       const u16x4 hi = *reinterpret_cast<const u16x4*>(Cs + rr * kCS + cg * 8 + 4);
       u16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      if constexpr (BASE == 5) {  // identity-branch gradient = dout * relu'(block output), from bits
+      if constexpr (BASE == kEpiAddMasked) {  // identity-branch gradient = dout * relu'(block output), from bits
         v = bf16_add_where(v, ra[i], rb[i]);
-      } else if constexpr (BASE == 2 || BASE == 4) {
-        if (BASE == 2 || !((rodd >> i) & 1u)) {
+      } else if constexpr (BASE == kEpiAdd || BASE == kEpiAddS2) {
+        if (BASE == kEpiAdd || !((rodd >> i) & 1u)) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = f32_to_bf16(bf16_to_f32(v[e]) + bf16_to_f32(ra[i][e]));
         }
-      } else if constexpr (EPI == 1) {
+      } else if constexpr (EPI == kEpiStats) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float d = bf16_to_f32(v[e]) - e0[e];
           s1[e] += d;
           s2[e] += d * d;
         }
-      } else if constexpr (EPI == 3) {
+      } else if constexpr (EPI == kEpiMaskSums) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float z = bf16_to_f32(ra[i][e]);
@@ -581,61 +577,41 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ConvGemmArgs p) 
 
 }  // namespace
 
-// the 256-channel-tile launches
-static void launch_big256(const ConvGemmArgs& a, hipStream_t s, bool bwd, bool resp) {
-  const int nblk = conv_big_gm(a.M) * (a.N / 256);
-#define PSAMD_BIG(E, P) hipLaunchKernelGGL((conv_big_kernel<E, P>), dim3(nblk), dim3(512), 0, s, a)
-  if (bwd) {
-    switch (a.epi) {
-      case 2: PSAMD_BIG(2, 2); break;
-      case 4: PSAMD_BIG(4, 2); break;
-      case 5: PSAMD_BIG(5, 2); break;
-      case 6: PSAMD_BIG(6, 2); break;
-      case 7: PSAMD_BIG(7, 2); break;
-      case 8: PSAMD_BIG(8, 2); break;
-      case 9: PSAMD_BIG(9, 2); break;
-      default: PSAMD_BIG(3, 2); break;
-    }
-  } else if (resp) {
-    if (a.epi == 1) PSAMD_BIG(1, 3);
-    else PSAMD_BIG(0, 3);
-  } else if (a.pro != nullptr) {
-    if (a.epi == 1) PSAMD_BIG(1, 1);
-    else PSAMD_BIG(0, 1);
-  } else {
-    switch (a.epi) {
-      case 1: PSAMD_BIG(1, 0); break;
-      case 2: PSAMD_BIG(2, 0); break;
-      case 3: PSAMD_BIG(3, 0); break;
-      case 4: PSAMD_BIG(4, 0); break;
-      case 5: PSAMD_BIG(5, 0); break;
-      case 6: PSAMD_BIG(6, 0); break;
-      case 7: PSAMD_BIG(7, 0); break;
-      case 8: PSAMD_BIG(8, 0); break;
-      case 9: PSAMD_BIG(9, 0); break;
-      default: PSAMD_BIG(0, 0); break;
-    }
+// launch_conv_big's instantiations: every pair that exists
+bool conv_big_runs(int pro, int epi) { return conv_pro_epi_exists(pro, epi); }
+
+void launch_conv_big(const ConvGemmArgs& a, hipStream_t s) {
+  const int nblk = conv_big_gm(a.M) * (a.N / 256), pro = conv_pro(a);
+#define PSAMD_BIG(P, E) hipLaunchKernelGGL((conv_big_kernel<E, P>), dim3(nblk), dim3(512), 0, s, a)
+#define PSAMD_BIG_EPIS(EPIS, P) \
+  switch (a.epi) { EPIS(PSAMD_BIG, P) default: conv_no_kernel(pro, a.epi); }
+  switch (pro) {
+    case kProBnBwd: PSAMD_BIG_EPIS(PSAMD_EPIS_DGRAD, kProBnBwd) break;
+    case kProBlockOut: PSAMD_BIG_EPIS(PSAMD_EPIS_FWD, kProBlockOut) break;
+    case kProBnRelu: PSAMD_BIG_EPIS(PSAMD_EPIS_FWD, kProBnRelu) break;
+    default: PSAMD_BIG_EPIS(PSAMD_EPIS_ALL, kProNone) break;
   }
+#undef PSAMD_BIG_EPIS
 #undef PSAMD_BIG
 }
 
 // Eligible: a 1x1 GEMM (rows in order) with K = C, N a multiple of 256, K >= 256, and >= 1024
-// blocks or K >= 1024 (with >= 256 blocks); epilogues 0 / 1 / 3 with or without a stride-1
-// prologue, the residual / fold epilogues 2, 4-9 without one (or with the BN backward one).
+// blocks or K >= 1024 (with >= 256 blocks); kEpiStore / kEpiStats / kEpiMaskSums with or without a
+// stride-1 prologue, the residual / fold epilogues without one (or with the BN backward one).
 int conv_big_tn(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int epi) {
   if (g.RH != 0) return 0;
   if (g.ks != 1 || g.ksw > 1 || g.pad != 0 || g.C != K) return 0;
-  if (epi < 0 || epi > 9) return 0;
+  if (!epi_valid(epi)) return 0;
   if (N % 256 != 0 || K % 64 != 0 || K < 256) return 0;
-  const bool plain_epi = epi == 0 || epi == 1 || epi == 3;
-  // the residual / fold epilogues (2, 4-9: the conv1 data gradients): no prologue, or the BN
-  // backward one (the conv1 data gradient with bn1's backward applied)
-  if (!plain_epi && ((pro && src2 != 2) || src2 == 1)) return 0;
-  // prologues (PRO 1: pro, src2 0; PRO 3: src2 1; PRO 2: src2 2 + a data-gradient epilogue): stride 1 only
-  if (pro || src2 != 0) {
+  const bool plain_epi = epi_is_fwd(epi) || epi == kEpiMaskSums;
+  // the residual / fold epilogues (the conv1 data gradients): no prologue, or the BN backward one
+  // (the conv1 data gradient with bn1's backward applied)
+  if (!plain_epi && ((pro && src2 != kSrc2BnBwd) || src2 == kSrc2BlockOut)) return 0;
+  // prologues (kProBnRelu: pro, no src2; kProBlockOut; kProBnBwd + a data-gradient epilogue): stride 1 only
+  if (pro || src2 != kSrc2None) {
     if (g.stride != 1) return 0;
-    if (src2 == 2 && (epi == 0 || epi == 1)) return 0;
-    if (src2 == 1 && epi == 3) return 0;
+    if (src2 == kSrc2BnBwd && epi_is_fwd(epi)) return 0;
+    if (src2 == kSrc2BlockOut && epi == kEpiMaskSums) return 0;
   }
   // one block per CU: below ~4 rounds of blocks the last round's idle CUs and the per-tile
   // prologue / epilogue outweigh the faster K loop unless K is deep (profiles/r5_conv_big_probe.txt:
@@ -644,15 +620,6 @@ int conv_big_tn(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int e
   return nblk >= 256 && (nblk >= 1024 || K >= 1024) ? 256 : 0;
 }
 
-bool conv_big_ok(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int epi) {
-  return conv_big_tn(M, N, K, pro, g, src2, epi) != 0;
-}
-
 int conv_big_gm(int M) { return (M + kTM - 1) / kTM; }
-
-void launch_conv_big(const ConvGemmArgs& a, hipStream_t s) {
-  const bool bwd = a.bwd != nullptr, resp = a.pro != nullptr && a.a2 != nullptr && !bwd;
-  launch_big256(a, s, bwd, resp);
-}
 
 }  // namespace psamd

@@ -4,7 +4,7 @@
 // Reference hot op: layer/Conv2DLayer.java:146-240 (a conv layer's backward = data gradient +
 // weight gradient of the same output gradient).  The unfused chain (ops/convgemm.py) ran
 //   dz3 = bf16(ca * g + cb * z3 + cc)          (bn3 backward: a two-source prologue that STORES dz3)
-//   gy2 = mask(dz3 W3) + bn2 backward sums     (conv3 data gradient, epilogue 3)
+//   gy2 = mask(dz3 W3) + bn2 backward sums     (conv3 data gradient, kEpiMaskSums)
 //   dW3 = dz3^T relu(bn2(z2))                  (a second kernel: re-reads dz3 and z2)
 // i.e. dz3 went to HBM and back ([M, CO] bf16 written + read) and z2 was read twice.  Here a
 // persistent block per CU builds dz3 in LDS one 64-channel stage at a time and feeds BOTH GEMMs
@@ -14,7 +14,7 @@
 // where a2 = relu(bf16(z2 sc2 + sh2)) is recomputed once per tile from the z2 tile in LDS (the
 // same tile gives the epilogue its ReLU mask and x-hat), the per-block dW accumulates in
 // registers over every tile of the block and leaves as ONE fp32 slab (fixed-order reduce), and
-// bn2's partial sums leave as [2][blocks][CI] like conv_gemm's epilogue 3.
+// bn2's partial sums leave as [2][blocks][CI] like conv_gemm's kEpiMaskSums.
 //
 // Streams per 128-pixel tile: g and z3 (2 x 128 x CO bf16) through a 3-slot LDS-DMA ring of
 // stage tiles (g lands by DMA, z3 by register loads one stage ahead, the BN-backward pass writes
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(512, 1) void conv11_bwd_fused_kernel(const Conv11Bw
         aw = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat8(dlo[k2], dhi[k2]), a2f[2 * h + k2], aw, 0, 0, 0);
     }
   };
-  // data-gradient epilogue of tile ti (the conv_gemm epi-3 arithmetic): bn2's ReLU mask from z2,
+  // data-gradient epilogue of tile ti (the conv_gemm kEpiMaskSums arithmetic): bn2's ReLU mask from z2,
   // the backward sums sum(g), sum(g (z2 - mean) invstd), masked gy out.  Register q of the lane is
   // pixel 32 pb + 8 (q >> 2) + 4 fh + (q & 3) of channel ec; its four z2 values per q >> 2 come from
   // ONE transposed read (each 16-lane group reads the 4 x 16 block of its rows / channels)

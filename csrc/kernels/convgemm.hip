@@ -14,18 +14,22 @@
 //               same GEMM on the transposed / flipped weight)
 //     prologue  f(a) = relu(a * scale_c + shift_c): the previous BN + ReLU applied while A is
 //               staged -- that BN's output is never written (taps outside the map stay 0)
-//     epilogue  1: per-channel partial sums of C about a shift (the next BN's statistics)
-//               2: + residual rows (block-input gradient = conv1 data grad + identity grad)
-//               3: ReLU mask from z*scale + shift and that BN's backward sums sum(g),
+//     epilogue  (psamd_launch.h ConvEpi)
+//               kEpiStats (1): per-channel partial sums of C about a shift (the next BN's statistics)
+//               kEpiAdd (2): + residual rows (block-input gradient = conv1 data grad + identity grad)
+//               kEpiMaskSums (3): ReLU mask from z*scale + shift and that BN's backward sums sum(g),
 //                  sum(g * xhat) -- its reduce pass
-//               4: + a stride-2 map's rows at even (h, w) (downsample data gradient)
-//               5: + residual rows masked by forward ReLU bits (identity gradient, never stored)
-//               6/7/8: epilogue 5/2/4, then the PREVIOUS block's bn3 backward reduce folded in:
+//               kEpiAddS2 (4): + a stride-2 map's rows at even (h, w) (downsample data gradient)
+//               kEpiAddMasked (5): + residual rows masked by forward ReLU bits (identity gradient,
+//                  never stored)
+//               kEpiFoldAddMasked / kEpiFoldAdd / kEpiFoldAddS2 (6/7/8): kEpiAddMasked / kEpiAdd /
+//                  kEpiAddS2, then the PREVIOUS block's bn3 backward reduce folded in:
 //                  g = v * relu'(previous block output) from its bits (stored masked) and the
 //                  sums sum(g), sum(g * (z3 - mean) * invstd) over that block's bn3 input z3
-//               9: epilogue 6 when the previous block has a downsample branch: its BN's backward
-//                  gets the same g, so a third sum sum(g * (zd - mean2) * invstd2) over the
-//                  downsample BN input zd replaces that BN's separate reduce pass
+//               kEpiFoldAddMaskedDs (9): kEpiFoldAddMasked when the previous block has a downsample
+//                  branch: its BN's backward gets the same g, so a third sum
+//                  sum(g * (zd - mean2) * invstd2) over the downsample BN input zd replaces that
+//                  BN's separate reduce pass
 //   conv_wgrad  dW[n, k] = sum_m dZ[m, n] f(A[src(m, k)]), split over m; both operands are read
 //               transposed from row-major LDS tiles (ds_read_b64_tr_b16); fp32 per-split slabs,
 //               fixed-order reduction (deterministic, no atomics).
@@ -219,8 +223,9 @@ struct StageRegs {
   bool wb;      // b[] loaded (to be staged)
 };
 
-// PRO: 0 none, 1 BN + ReLU of the A rows, 2 BN backward from two row sources (a, a2),
-// 3 the previous block's output relu(bn3(a) + r) with r = a2 (identity) or bnd(a2) (downsample)
+// PRO (psamd_launch.h ConvPro): kProNone, kProBnRelu BN + ReLU of the A rows, kProBnBwd BN backward
+// from two row sources (a, a2), kProBlockOut the previous block's output relu(bn3(a) + r) with
+// r = a2 (identity) or bnd(a2) (downsample)
 // PATCH (3x3 / stride 1 / pad 1, LDS-DMA path): the tile's input rows -- a PATCH of whole rows with
 // zero halo rows / columns, at most two images -- are staged ONCE per 64-channel chunk and the nine
 // taps read their A fragments from it at a shifted slot; a K stage then moves only its weight tile.
@@ -236,26 +241,27 @@ constexpr int patch_bytes() { return BN == 64 ? 65536 : 40960; }  // 8 channel p
 // (one GEMM per launch) or conv_dgrad_phases_kernel (the four stride-2 data-gradient phases in one grid).
 template <int BM, int BN, int PRO, int EPI, bool KS1, bool GLDS, int VAR = 0>
 __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int L) {
-  constexpr bool BWD = PRO == 2;
-  constexpr bool RESP = PRO == 3;
-  static_assert(!BWD || (KS1 && EPI == 3), "the BN-backward prologue is a 1x1 data-gradient prologue");
-  static_assert(!RESP || (KS1 && EPI <= 1), "the block-output prologue is a 1x1 forward prologue");
+  constexpr bool BWD = PRO == kProBnBwd;
+  constexpr bool RESP = PRO == kProBlockOut;
+  static_assert(conv_pro_epi_exists(PRO, EPI), "conv_gemm's (prologue, epilogue) pairs");
+  static_assert(!BWD || (KS1 && EPI == kEpiMaskSums), "the BN-backward prologue is a 1x1 data-gradient prologue");
+  static_assert(!RESP || KS1, "the block-output prologue is a 1x1 forward prologue");
   // two-source prologues on the LDS-DMA path: both row sources land in LDS by DMA and one pass
   // over the stage tile applies the prologue in place (a single third buffer for the second
   // source: it is refilled once the pass has read it)
   constexpr bool TWO_GLDS = GLDS && (BWD || RESP);
-  // PRO 1 (BN + ReLU of A) on the LDS-DMA path: the same in-place pass, one source (1x1 only:
+  // kProBnRelu (BN + ReLU of A) on the LDS-DMA path: the same in-place pass, one source (1x1 only:
   // the pass cannot tell a 3x3 halo slot's zero from a real 0)
-  constexpr bool ONE_GLDS = GLDS && PRO == 1;
+  constexpr bool ONE_GLDS = GLDS && PRO == kProBnRelu;
   static_assert(!ONE_GLDS || KS1, "the LDS-pass BN prologue is for 1x1 convolutions");
   constexpr bool XF_GLDS = TWO_GLDS || ONE_GLDS;
   constexpr int AR2 = BWD || RESP ? BM / 32 : 1;
-  // epilogues 6/7/8 = base epilogue 5/2/4 + the previous block's bn3 backward reduce; 9 = 6 + the
-  // previous block's downsample-BN sum (third partial slab)
-  constexpr bool FOLD = EPI >= 6;
-  constexpr bool FOLD_DS = EPI == 9;
-  constexpr int BASE = EPI == 6 || EPI == 9 ? 5 : EPI == 7 ? 2 : EPI == 8 ? 4 : EPI;
-  constexpr int NSUM = FOLD_DS ? 3 : 2;
+  // the fold epilogues = a base epilogue + the previous block's bn3 backward reduce (+ its
+  // downsample-BN sum, a third partial slab): psamd_launch.h ConvEpi
+  constexpr bool FOLD = epi_folds(EPI);
+  constexpr bool FOLD_DS = epi_folds_ds(EPI);
+  constexpr int BASE = epi_base(EPI);
+  constexpr int NSUM = epi_sum_slabs(EPI);
   // waves 2 x 2 over the tile; the tall 256 x 64 tile (LDS-DMA path only) stacks them 4 x 1 so
   // every wave still computes 64 x 64 (a 128 x 64 tile gave each wave 64 x 32: 1.5 fragment
   // reads per MFMA instead of 1, and half the weight-tile reuse)
@@ -271,7 +277,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
   constexpr int CS = BN + 4;
   // LDS: [A0 | A1] overlaid by the output tile + statistics scratch, then [B0 | B1] (never
   // overlaid, so a resident weight tile survives the epilogues)
-  // EPI 9 keeps its third running sum in LDS (8 floats per thread past the output tile): in
+  // kEpiFoldAddMaskedDs keeps its third running sum in LDS (8 floats per thread past the output tile): in
   // registers it pushed the register-staged variant from 20 to 76 B/lane of scratch
   constexpr int RED_ELEMS = 4 * NSUM * BN * 2 > (FOLD_DS ? 256 * 8 * 2 : 0) ? 4 * NSUM * BN * 2 : 256 * 8 * 2;
   constexpr int EPI_ELEMS = BM * CS + RED_ELEMS;
@@ -362,7 +368,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
     uint16_t* As = lds + buf * (BM * kBK);
     uint16_t* Bs = lds + B_BASE + buf * (BN * kBK);
     float psc[8], psh[8], pcf[8], pdd[8];
-    if constexpr (PRO == 1 || RESP) {  // [scale | shift] of 8 channels: L1-resident
+    if constexpr (PRO == kProBnRelu || RESP) {  // [scale | shift] of 8 channels: L1-resident
       load8(p.pro, R.cc + sc * 8, psc);
       load8(p.pro + g.C, R.cc + sc * 8, psh);
     } else if constexpr (BWD) {  // [ca | cb | cc]
@@ -381,7 +387,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
       u16x8 v = R.a[i];
-      if constexpr (PRO == 1) v = bn_relu8(v, psc, psh);
+      if constexpr (PRO == kProBnRelu) v = bn_relu8(v, psc, psh);
       if constexpr (BWD) {
         const u16x8 x8 = R.a2[i];
 #pragma unroll
@@ -463,14 +469,14 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
   float s1[8], s2[8], e0[8], e1[8], e2[8], e3[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = e0[j] = e1[j] = e2[j] = e3[j] = 0.f;
-  float* s3l = reinterpret_cast<float*>(lds + BM * CS) + t * 8;  // EPI 9: this thread's third sum
+  float* s3l = reinterpret_cast<float*>(lds + BM * CS) + t * 8;  // FOLD_DS: this thread's third sum
   if constexpr (FOLD_DS) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) s3l[j] = 0.f;
   }
-  if constexpr (EPI == 1) {
+  if constexpr (EPI == kEpiStats) {
     if (p.kshift) load8(p.kshift, nc, e0);
-  } else if constexpr (EPI == 3) {
+  } else if constexpr (EPI == kEpiMaskSums) {
     load8(p.mc, nc, e0);
     load8(p.mc + p.N, nc, e1);
     load8(p.mean, nc, e2);
@@ -485,18 +491,18 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
   // data-gradient epilogues ran at ~2.8 TB/s).  Rows past M read row M - 1 (in bounds, unused).
   constexpr int NPASS = BM / RPP;
   // destination row of output pixel m (a stride-2 data-gradient phase scatters to every other row)
-  // (only the phase launches -- epilogues 0 / 3, bindings conv_dgrad_s2 -- carry RH > 0: the
-  // other epilogues compile the scatter away)
+  // (only the phase launches -- kEpiStore / kEpiMaskSums, bindings conv_dgrad_s2 -- carry RH > 0:
+  // the other epilogues compile the scatter away)
   auto orow = [&](int m) -> int64_t {
-    if (!(EPI == 0 || EPI == 3) || g.RH == 0) return m;
+    if (!(EPI == kEpiStore || EPI == kEpiMaskSums) || g.RH == 0) return m;
     const int ohw = g.OH * g.OW, im = static_cast<int>(fdiv(static_cast<uint32_t>(m), p.fd_ohw)), r = m - im * ohw,
               i = static_cast<int>(fdiv(static_cast<uint32_t>(r), p.fd_ow)), j = r - i * g.OW;
     return (static_cast<int64_t>(im) * g.RH + 2 * i + g.ra) * g.RW + 2 * j + g.rb;
   };
-  constexpr bool RD_AUX = BASE == 5 || BASE == 2 || BASE == 4 || EPI == 3;
+  constexpr bool RD_AUX = epi_reads_aux(EPI);
   u16x8 ra[RD_AUX ? NPASS : 1], rz[FOLD ? NPASS : 1];
-  unsigned rb[BASE == 5 ? NPASS : 1], rp[FOLD ? NPASS : 1];
-  unsigned rodd = 0;  // BASE 4: rows without a residual (odd h or w)
+  unsigned rb[epi_needs_bits(EPI) ? NPASS : 1], rp[FOLD ? NPASS : 1];
+  unsigned rodd = 0;  // kEpiAddS2: rows without a residual (odd h or w)
   auto epi_load = [&](int mt) {
     const int m0 = mt * BM;
     rodd = 0;
@@ -504,7 +510,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
     for (int i = 0; i < NPASS; ++i) {
       const int m = min(m0 + r0 + i * RPP, p.M - 1);
       const int64_t o = orow(m) * p.N + nc;
-      if constexpr (BASE == 4) {  // residual map (OH+1)/2 x (OW+1)/2, present at even (h, w)
+      if constexpr (BASE == kEpiAddS2) {  // residual map (OH+1)/2 x (OW+1)/2, present at even (h, w)
         const int ohw = g.OH * g.OW;
         const int im = static_cast<int>(fdiv(static_cast<uint32_t>(m), p.fd_ohw)), r = m - im * ohw,
                   h = static_cast<int>(fdiv(static_cast<uint32_t>(r), p.fd_ow)), w = r - h * g.OW;
@@ -517,7 +523,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
       } else if constexpr (RD_AUX) {
         ra[i] = *reinterpret_cast<const u16x8*>(p.aux + o);
       }
-      if constexpr (BASE == 5) rb[i] = p.bits[o >> 3];
+      if constexpr (BASE == kEpiAddMasked) rb[i] = p.bits[o >> 3];
       if constexpr (FOLD) {
         rz[i] = *reinterpret_cast<const u16x8*>(p.aux2 + o);
         rp[i] = p.bits2[o >> 3];
@@ -550,22 +556,22 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
       const u16x4 hi = *reinterpret_cast<const u16x4*>(Cs + rr * CS + cg * 8 + 4);
       u16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       const int64_t o = orow(m) * p.N + nc;
-      if constexpr (BASE == 5) {  // identity-branch gradient = dout * relu'(block output), from bits
+      if constexpr (BASE == kEpiAddMasked) {  // identity-branch gradient = dout * relu'(block output), from bits
         v = bf16_add_where(v, ra[i], rb[i]);
-      } else if constexpr (BASE == 2 || BASE == 4) {
-        if (BASE == 2 || !((rodd >> i) & 1u)) {
+      } else if constexpr (BASE == kEpiAdd || BASE == kEpiAddS2) {
+        if (BASE == kEpiAdd || !((rodd >> i) & 1u)) {
           const u16x8 r8 = ra[i];
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = f32_to_bf16(bf16_to_f32(v[j]) + bf16_to_f32(r8[j]));
         }
-      } else if constexpr (EPI == 1) {
+      } else if constexpr (EPI == kEpiStats) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float d = bf16_to_f32(v[j]) - e0[j];
           s1[j] += d;
           s2[j] += d * d;
         }
-      } else if constexpr (EPI == 3) {
+      } else if constexpr (EPI == kEpiMaskSums) {
         const u16x8 z8 = ra[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -594,7 +600,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
       }
     }
   };
-  // EPI 9: second pass over the same rows once the first pass's row registers are dead (the
+  // kEpiFoldAddMaskedDs: second pass over the same rows once the first pass's row registers are dead (the
   // register-staged variant sits at the 256-VGPR budget): the downsample BN input rows zd, then
   // sum(g * (zd - mean2) * invstd2) with g read back from the thread's own tile slots
   auto epilogue_ds = [&](int mt) {
@@ -956,7 +962,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
     }
   }
 
-  if constexpr (EPI == 1 || EPI == 3 || FOLD) {
+  if constexpr (epi_writes_sums(EPI)) {
     float s3[FOLD_DS ? 8 : 1];
     if constexpr (FOLD_DS) {
 #pragma unroll
@@ -1012,7 +1018,7 @@ struct ConvPhaseArgs {
 
 template <int BN, int EPI>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_phases_kernel(const ConvPhaseArgs P) {
-  static_assert(EPI == 0 || EPI == 3, "plain store or the ReLU-mask + BN-backward-sums epilogue");
+  static_assert(EPI == kEpiStore || EPI == kEpiMaskSums, "plain store or the ReLU-mask + BN-backward-sums epilogue");
   const int b = blockIdx.x;
   const int i = b >= P.start[3] ? 3 : b >= P.start[2] ? 2 : b >= P.start[1] ? 1 : 0;
   const int ph = P.order[i];
@@ -1771,12 +1777,8 @@ bool patch_fwd_ok(const ConvGeo& g, int N, bool pro) {
   return 8 * plane <= (bn == 64 ? patch_bytes<64>() : patch_bytes<128>());
 }
 
-// two-source prologues with K >= 64 x this run on the LDS-DMA variant (profiles/r4_twosrc_probe.txt:
-// LDS-DMA ahead at every K >= 256)
-constexpr int kTwosrcGldsMinNk = 4;
-
-// src2: two-source prologue of the launch (0 none, 1 block output, 2 BN backward)
-bool twosrc_glds(int K, int src2) { return src2 != 0 && K / kBK >= kTwosrcGldsMinNk; }
+// src2: two-source prologue of the launch (ConvSrc2); deep K runs on the LDS-DMA variant
+bool twosrc_glds(int K, int src2) { return src2 != kSrc2None && K / kBK >= kTwosrcGldsMinNk; }
 
 ConvFwdPlan conv_fwd_plan_geo(int M, int N, int K, bool pro, const ConvGeo& g, int src2, int epi) {
   if (const int tn = conv_big_tn(M, N, K, pro, g, src2, epi)) {  // 256 x TN tiles (conv_big.hip)
@@ -1793,7 +1795,7 @@ ConvFwdPlan conv_fwd_plan_geo(int M, int N, int K, bool pro, const ConvGeo& g, i
     pl.gm = (M + 127) / 128;
     return pl;
   }
-  if (src2 == 1) {  // block-output prologue: 64-channel tiles (128 x 128 with two row sources spilled)
+  if (src2 == kSrc2BlockOut) {  // block-output prologue: 64-channel tiles (128 x 128 with two row sources spilled)
     ConvFwdPlan pl = conv_fwd_plan(M, N, K, true);
     pl.bn = 64;
     if (pl.gm != (M + 127) / 128) pl.gm = std::max(1, std::min((M + 127) / 128, 512 / (N / 64)));
@@ -1828,45 +1830,61 @@ ConvFwdPlan conv_fwd_plan(int M, int N, int K, bool pro, int epi) {
   return pl;
 }
 
+// What launch_conv_fwd's ladders instantiate for the tile family of a plan: the 256 x 256 tiles
+// every pair, the 128-pixel tiles the BN-backward prologue with kEpiMaskSums only, the tall
+// 256 x 64 tile (no prologue) all but kEpiFoldAddMaskedDs.
+bool conv_fwd_runs(const ConvFwdPlan& pl, int pro, int epi) {
+  if (!conv_pro_epi_exists(pro, epi)) return false;
+  if (pl.bm == 256 && pl.bn == 256) return conv_big_runs(pro, epi);
+  if (pro == kProBnBwd) return epi == kEpiMaskSums;
+  if (pl.bm == 256) return pro == kProNone && !epi_folds_ds(epi);
+  return true;
+}
+
 void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
   if (a0.M <= 0) return;
   ConvGemmArgs a = a0;
   a.fd_ohw = make_fastdiv(static_cast<uint32_t>(a.g.OH * a.g.OW));
   a.fd_ow = make_fastdiv(static_cast<uint32_t>(a.g.OW));
-  const bool bwd = a.bwd != nullptr;
-  const bool resp = a.pro != nullptr && a.a2 != nullptr && !bwd;
-  const int src2 = resp ? 1 : bwd ? 2 : 0;
-  const ConvFwdPlan pl = conv_fwd_plan_geo(a.M, a.N, a.K, a.pro != nullptr || bwd, a.g, src2, a.epi);
+  const int pro = conv_pro(a), src2 = pro_src2(pro);
+  const bool bwd = pro == kProBnBwd, resp = pro == kProBlockOut;
+  const ConvFwdPlan pl = conv_fwd_plan_geo(a.M, a.N, a.K, pro != kProNone, a.g, src2, a.epi);
+  if (!conv_fwd_runs(pl, pro, a.epi)) conv_no_kernel(pro, a.epi);
   const int GM = pl.gm;
   const int nblk = GM * (a.N / pl.bn);
-  if (conv_big_ok(a.M, a.N, a.K, a.pro != nullptr || bwd, a.g, src2, a.epi)) {
+  if (pl.bm == 256 && pl.bn == 256) {
     launch_conv_big(a, s);
     return;
   }
+// one epilogue ladder (psamd_launch.h PSAMD_EPIS_*) per channel tile: L(BN, args, epilogue)
+#define PSAMD_BN_EPIS(EPIS, L, ...)                                                       \
+  if (pl.bn == 128) {                                                                     \
+    switch (a.epi) { EPIS(L, 128, __VA_ARGS__) default: conv_no_kernel(pro, a.epi); }     \
+  } else {                                                                                \
+    switch (a.epi) { EPIS(L, 64, __VA_ARGS__) default: conv_no_kernel(pro, a.epi); }      \
+  }
+#define PSAMD_EPIS_MASKSUMS(L, ...) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__)
   if (twosrc_glds(a.K, src2)) {  // (1x1: the binding checks)
 #define PSAMD_CF2S(BN, PRO, EPI) \
   hipLaunchKernelGGL((conv_fwd_kernel<128, BN, PRO, EPI, true, true>), dim3(nblk), dim3(256), 0, s, a, GM)
     if (resp) {
-      if (pl.bn == 128) {
-        if (a.epi == 1) { PSAMD_CF2S(128, 3, 1); } else { PSAMD_CF2S(128, 3, 0); }
-      } else {
-        if (a.epi == 1) { PSAMD_CF2S(64, 3, 1); } else { PSAMD_CF2S(64, 3, 0); }
-      }
+      PSAMD_BN_EPIS(PSAMD_EPIS_FWD, PSAMD_CF2S, kProBlockOut)
     } else {
-      if (pl.bn == 128) { PSAMD_CF2S(128, 2, 3); } else { PSAMD_CF2S(64, 2, 3); }
+      PSAMD_BN_EPIS(PSAMD_EPIS_MASKSUMS, PSAMD_CF2S, kProBnBwd)
     }
 #undef PSAMD_CF2S
     return;
   }
-  if (!bwd && patch_fwd_ok(a.g, a.N, a.pro != nullptr) && (a.epi == 0 || a.epi == 1 || a.epi == 3)) {
-#define PSAMD_CFP(BN, EPI) \
-  hipLaunchKernelGGL((conv_fwd_kernel<128, BN, 0, EPI, false, true, true>), dim3(nblk), dim3(256), 0, s, a, GM)
-    if (pl.bn == 128) {
-      if (a.epi == 1) { PSAMD_CFP(128, 1); } else if (a.epi == 3) { PSAMD_CFP(128, 3); } else { PSAMD_CFP(128, 0); }
-    } else {
-      if (a.epi == 1) { PSAMD_CFP(64, 1); } else if (a.epi == 3) { PSAMD_CFP(64, 3); } else { PSAMD_CFP(64, 0); }
-    }
+  // the 3x3 patch-staged tiles; the other epilogues run the im2col ladders below
+  if (pro == kProNone && patch_fwd_ok(a.g, a.N, false) && (epi_is_fwd(a.epi) || a.epi == kEpiMaskSums)) {
+#define PSAMD_EPIS_PATCH(L, ...)                                                              \
+  PSAMD_EPI_CASE(L, kEpiStats, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__)      \
+  PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
+#define PSAMD_CFP(BN, PRO, EPI) \
+  hipLaunchKernelGGL((conv_fwd_kernel<128, BN, PRO, EPI, false, true, 1>), dim3(nblk), dim3(256), 0, s, a, GM)
+    PSAMD_BN_EPIS(PSAMD_EPIS_PATCH, PSAMD_CFP, kProNone)
 #undef PSAMD_CFP
+#undef PSAMD_EPIS_PATCH
     return;
   }
   const bool ks1 = a.g.ks == 1 && a.g.ksw <= 1;
@@ -1875,70 +1893,45 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
 #define PSAMD_CF3(BM, BN, PRO, EPI, GL)                                                                          \
   if (ks1) hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, PRO, EPI, true, GL>), dim3(nblk), dim3(256), 0, s, a, GM); \
   else hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, PRO, EPI, false, GL>), dim3(nblk), dim3(256), 0, s, a, GM)
-#define PSAMD_CF2(BM, BN, PRO, EPI)                        \
-  if constexpr (PRO) { PSAMD_CF3(BM, BN, PRO, EPI, false); } \
-  else if (glds) { PSAMD_CF3(BM, BN, PRO, EPI, true); }       \
-  else { PSAMD_CF3(BM, BN, PRO, EPI, false); }
-#define PSAMD_CF(BN, PRO, EPI) PSAMD_CF2(128, BN, PRO, EPI)
-#define PSAMD_CFE(BN, PRO)               \
-  switch (a.epi) {                       \
-    case 1: PSAMD_CF(BN, PRO, 1); break; \
-    case 2: PSAMD_CF(BN, PRO, 2); break; \
-    case 3: PSAMD_CF(BN, PRO, 3); break; \
-    case 4: PSAMD_CF(BN, PRO, 4); break; \
-    case 5: PSAMD_CF(BN, PRO, 5); break; \
-    case 6: PSAMD_CF(BN, PRO, 6); break; \
-    case 7: PSAMD_CF(BN, PRO, 7); break; \
-    case 8: PSAMD_CF(BN, PRO, 8); break; \
-    case 9: PSAMD_CF(BN, PRO, 9); break; \
-    default: PSAMD_CF(BN, PRO, 0); break; \
-  }
+#define PSAMD_CF(BN, PRO, EPI)                                            \
+  if constexpr (PRO != kProNone) { PSAMD_CF3(128, BN, PRO, EPI, false); } \
+  else if (glds) { PSAMD_CF3(128, BN, PRO, EPI, true); }                  \
+  else { PSAMD_CF3(128, BN, PRO, EPI, false); }
   if (pl.bm == 256) {  // LDS-DMA only (no prologue, deep K)
-#define PSAMD_CFT(EPI) PSAMD_CF3(256, 64, false, EPI, true)
-    switch (a.epi) {
-      case 1: PSAMD_CFT(1); break;
-      case 2: PSAMD_CFT(2); break;
-      case 3: PSAMD_CFT(3); break;
-      case 4: PSAMD_CFT(4); break;
-      case 5: PSAMD_CFT(5); break;
-      case 6: PSAMD_CFT(6); break;
-      case 7: PSAMD_CFT(7); break;
-      case 8: PSAMD_CFT(8); break;
-      default: PSAMD_CFT(0); break;
-    }
+#define PSAMD_CFT(BN, EPI) PSAMD_CF3(256, BN, kProNone, EPI, true)
+    switch (a.epi) { PSAMD_EPIS_NO_DS(PSAMD_CFT, 64) default: conv_no_kernel(pro, a.epi); }
 #undef PSAMD_CFT
     return;
   }
-  if (resp) {  // 1x1 forward over the previous block's output, applied while staging
-#define PSAMD_CFR(BN, EPI) \
-  hipLaunchKernelGGL((conv_fwd_kernel<128, BN, 3, EPI, true, false>), dim3(nblk), dim3(256), 0, s, a, GM)
-    if (pl.bn == 128) {
-      if (a.epi == 1) { PSAMD_CFR(128, 1); } else { PSAMD_CFR(128, 0); }
-    } else {
-      if (a.epi == 1) { PSAMD_CFR(64, 1); } else { PSAMD_CFR(64, 0); }
+  if (resp || bwd) {  // the register-staged two-source prologues (1x1, shallow K)
+#define PSAMD_CFR(BN, PRO, EPI) \
+  hipLaunchKernelGGL((conv_fwd_kernel<128, BN, PRO, EPI, true, false>), dim3(nblk), dim3(256), 0, s, a, GM)
+    if (resp) {  // forward over the previous block's output, applied while staging
+      PSAMD_BN_EPIS(PSAMD_EPIS_FWD, PSAMD_CFR, kProBlockOut)
+    } else {  // data gradient with the previous BN's backward in the prologue
+      PSAMD_BN_EPIS(PSAMD_EPIS_MASKSUMS, PSAMD_CFR, kProBnBwd)
     }
 #undef PSAMD_CFR
     return;
   }
-  if (bwd) {  // 1x1 data gradient with the previous BN's backward in the prologue (epilogue 3)
-    if (pl.bn == 128) hipLaunchKernelGGL((conv_fwd_kernel<128, 128, 2, 3, true, false>), dim3(nblk), dim3(256), 0, s, a, GM);
-    else hipLaunchKernelGGL((conv_fwd_kernel<128, 64, 2, 3, true, false>), dim3(nblk), dim3(256), 0, s, a, GM);
-    return;
-  }
-  // the BN prologue only appears on forward convolutions (epilogue 0 / 1)
+  // the BN prologue only appears on forward convolutions
   if (pl.bn == 128) {
     if (a.pro) {
-      if (a.epi == 1) { PSAMD_CF(128, true, 1); } else { PSAMD_CF(128, true, 0); }
-    } else { PSAMD_CFE(128, false) }
+      switch (a.epi) { PSAMD_EPIS_FWD(PSAMD_CF, 128, kProBnRelu) default: conv_no_kernel(pro, a.epi); }
+    } else {
+      switch (a.epi) { PSAMD_EPIS_ALL(PSAMD_CF, 128, kProNone) default: conv_no_kernel(pro, a.epi); }
+    }
   } else {
     if (a.pro) {
-      if (a.epi == 1) { PSAMD_CF(64, true, 1); } else { PSAMD_CF(64, true, 0); }
-    } else { PSAMD_CFE(64, false) }
+      switch (a.epi) { PSAMD_EPIS_FWD(PSAMD_CF, 64, kProBnRelu) default: conv_no_kernel(pro, a.epi); }
+    } else {
+      switch (a.epi) { PSAMD_EPIS_ALL(PSAMD_CF, 64, kProNone) default: conv_no_kernel(pro, a.epi); }
+    }
   }
-#undef PSAMD_CFE
 #undef PSAMD_CF
-#undef PSAMD_CF2
 #undef PSAMD_CF3
+#undef PSAMD_EPIS_MASKSUMS
+#undef PSAMD_BN_EPIS
 }
 
 int conv_dgrad_phase_gm(int M) { return (M + 127) / 128; }
@@ -1961,15 +1954,19 @@ void launch_conv_dgrad_phases(const ConvGemmArgs* ph, hipStream_t s) {
   }
   P.start[4] = at;
   if (at == 0) return;
-  const bool e3 = ph[0].epi == 3;  // (the binding allows 0 or 3 and sets the part / aux / mc of epi 3)
+#define PSAMD_DP(BN, EPI) hipLaunchKernelGGL((conv_dgrad_phases_kernel<BN, EPI>), dim3(at), dim3(256), 0, s, P)
+#define PSAMD_EPIS_PHASES(L, ...) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
+  // (the binding sets the part / aux / mc of kEpiMaskSums)
   if (bn == 128) {
-    if (e3) hipLaunchKernelGGL((conv_dgrad_phases_kernel<128, 3>), dim3(at), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((conv_dgrad_phases_kernel<128, 0>), dim3(at), dim3(256), 0, s, P);
+    switch (ph[0].epi) { PSAMD_EPIS_PHASES(PSAMD_DP, 128) default: conv_no_kernel(kProNone, ph[0].epi); }
   } else {
-    if (e3) hipLaunchKernelGGL((conv_dgrad_phases_kernel<64, 3>), dim3(at), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((conv_dgrad_phases_kernel<64, 0>), dim3(at), dim3(256), 0, s, P);
+    switch (ph[0].epi) { PSAMD_EPIS_PHASES(PSAMD_DP, 64) default: conv_no_kernel(kProNone, ph[0].epi); }
   }
+#undef PSAMD_EPIS_PHASES
+#undef PSAMD_DP
 }
+
+bool conv_dgrad_phases_runs(int epi) { return epi == kEpiStore || epi == kEpiMaskSums; }
 
 namespace {
 struct WPlan {
@@ -2075,6 +2072,8 @@ void slab_reduce(const ConvWgradArgs& a, int nsplit, int groups, hipStream_t s) 
   }
 }
 }  // namespace
+
+bool conv_wgrad_patch_ok(const ConvGeo& g, int M, int N, bool pro) { return patch_ok(g, M, N, pro); }
 
 int64_t conv_wgrad_ws_geo(int M, int N, int K, const ConvGeo& g, bool pro) {
   if (patch_ok(g, M, N, pro)) {

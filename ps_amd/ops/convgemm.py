@@ -23,7 +23,7 @@ MFMA GEMMs with the neighbouring BatchNorm passes folded into them:
             epilogue), weight grads.
 
 Across blocks: block i's conv1 data-grad epilogue also runs block i-1's bn3 backward reduce
-(epilogues 6/7/8: mask by block i-1's output bits, sums against its z3), so block i-1's bn3
+(the Epi.FOLD_* epilogues: mask by block i-1's output bits, sums against its z3), so block i-1's bn3
 backward is one apply pass -- or, at 256 channels, no pass at all: block i-1's conv3 data-grad GEMM
 applies it while staging its A tile from (gradient, z3) and stores dz3 for the weight gradient.  The hand-off is a ``_Link`` set up in forward when block i's input
 IS block i-1's output; block i-1 uses the partials only if the gradient it receives is exactly
@@ -40,6 +40,7 @@ oracle in tests/test_convgemm_gpu.py.  ``PS_AMD_DISABLE=fused_block`` turns the 
 from __future__ import annotations
 
 import contextlib
+import enum
 import threading
 import weakref
 from typing import List
@@ -71,20 +72,28 @@ def geo(h: int, w: int, ks: int = 1, stride: int = 1, pad: int = 0) -> List[int]
     return [h, w, (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1, ks, stride, pad]
 
 
-def conv_gemm(a, b, g, pro=None, epi=0, aux=None, kshift=None, mc=None, mean=None, invstd=None, bits=None):
-    """c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> (c, folded BN partials [2, G, N] or None).
+class Epi(enum.IntEnum):
+    """Epilogues of ``native().conv_gemm`` (csrc/include/psamd_launch.h ConvEpi; ``native().EPI``):
+    c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> (c, BN partials [2 or 3, G, N] or None)."""
 
-    a: [images*H*W, C] bf16 rows; b: [N, ks*ks*C] (channels_last weight order; a strided view is
-    copied contiguous once); g: ``geo(...)``;
-    pro: [scale | shift] applied with ReLU to ``a`` while staging; epi: 0 store, 1 + BN statistics
-    (about ``kshift``), 2 + ``aux`` rows, 3 ReLU mask from ``aux`` * mc + shift and BN-backward sums,
-    4 + ``aux`` of the stride-2 map at even (h, w), 5 + ``aux`` masked by ReLU ``bits``."""
-    return native().conv_gemm(a, b, g, pro, epi, aux, kshift, mc, mean, invstd, bits)
+    STORE = 0
+    STATS = 1               # + BN statistics of c about ``kshift``
+    ADD = 2                 # + ``aux`` rows
+    MASK_SUMS = 3           # ReLU mask from ``aux`` * mc + shift and that BN's backward sums
+    ADD_S2 = 4              # + ``aux`` of the stride-2 map at even (h, w)
+    ADD_MASKED = 5          # + ``aux`` masked by ReLU ``bits``
+    FOLD_ADD_MASKED = 6     # ADD_MASKED / ADD / ADD_S2 + the producer block's bn3 backward reduce
+    FOLD_ADD = 7            # (``aux2``, ``bits2``, ``mean``, ``invstd``)
+    FOLD_ADD_S2 = 8
+    FOLD_ADD_MASKED_DS = 9  # FOLD_ADD_MASKED + the producer's downsample-BN sum (``aux3``, ``mean2``, ``invstd2``)
 
 
-def conv_wgrad(dz, x, g, pro=None):
-    """dW [N, ks*ks*C] bf16 = sum_m dz[m]^T f(x[src(m, k)])."""
-    return native().conv_wgrad(dz, x, g, pro)
+class Src2(enum.IntEnum):
+    """Two-source prologue of a conv_gemm launch, as ``native().conv_gemm_plan`` takes it."""
+
+    NONE = 0
+    BLOCK_OUT = 1  # pro + a2: the producer block's output relu(bn3(a) + r)
+    BN_BWD = 2     # bwd + a2: the previous BN's backward
 
 
 def _momentum(bn: nn.BatchNorm2d) -> float:
@@ -143,26 +152,23 @@ def _phase_weights(w: torch.Tensor) -> List[torch.Tensor]:
     return out
 
 
-def _dgrad_s2_min_c() -> int:
-    """Stride-2 data gradients on the phase GEMMs from 128 channels up: at 256 / 512 channels they
-    beat MIOpen's kernel alone; at 128 (56x56) the four phases (747 us) trail its kernel (728 us)
-    but not its zero fill + the separate bn1 reduce (profiles/r2_probe_dgrad_s2.jsonl: bench A/B
-    13.53-13.56K vs 13.52K img/s)."""
-    return 128
-
+# Stride-2 data gradients on the phase GEMMs from 128 channels up: at 256 / 512 channels they
+# beat MIOpen's kernel alone; at 128 (56x56) the four phases (747 us) trail its kernel (728 us)
+# but not its zero fill + the separate bn1 reduce (profiles/r2_probe_dgrad_s2.jsonl: bench A/B
+# 13.53-13.56K vs 13.52K img/s).
+DGRAD_S2_MIN_C = 128
 
 WGRAD3X3_MIN_C = 256
 
+# Two-source prologues pay while the GEMM has ONE channel tile (N <= 128): every further tile
+# re-reads both row sources (scripts/probe_twosrc.py, profiles/r4_twosrc_probe.txt: conv3 data
+# grad 0.51 vs 0.64 ms at N = 128, 0.36 vs 0.25 ms at N = 512).
+TWOSRC_MAX_N = 128
 
-def _patch_wgrad_ok(h: int, w: int, c1: int, c2: int, s: int) -> bool:
-    """The shapes csrc conv_wgrad_patch_kernel takes (mirrors convgemm.hip patch_ok): 3x3 / pad 1,
-    stride 1 on 56- or 28-wide input maps, stride 2 on a 56-wide one (whole 112-pixel stages),
-    c1 <= 128."""
-    if not (c1 % 64 == 0 and c2 % 64 == 0 and c1 <= 128):
-        return False
-    if s == 1:
-        return w in (56, 28) and h % (112 // w) == 0
-    return s == 2 and w == 56 and h % 8 == 0
+# conv3's forward applies bn2 + ReLU while staging up to this many input channels; deeper
+# (layer 4, 512) the apply pass + plain GEMM is faster: 0.16 vs 0.21 ms (layer 3: 0.26 either
+# way; profiles/r4_twosrc_probe.txt, bn_relu_prologue rows).
+PRO_FUSE_MAX_K = 256
 
 
 def _conv3x3_enabled() -> bool:
@@ -179,7 +185,7 @@ class _Link:
         self.out_ref = None
         self.z3, self.bits, self.mean, self.invstd = z3, bits, mean, invstd
         # a downsample block also hands its downsample BN (input zd, batch stats): the consumer's
-        # epilogue 9 reduces that BN's backward sum next to bn3's
+        # Epi.FOLD_ADD_MASKED_DS reduces that BN's backward sum next to bn3's
         self.zd, self.md, self.idd = zd, md, idd
         self.part = None
         self.dx_ptr = self.dx_version = self.dx_keep = None
@@ -192,7 +198,7 @@ FOLD_STATS = {"used": 0, "ds": 0, "resp": 0}  # bn3 / downsample-BN backward pas
 class _Deferred:
     """A block output left unapplied: relu(bn3(z3) + r), r = the block input (identity) or the
     downsample BN's output.  The next fused block's conv1 applies it while staging its A tile and
-    writes the output rows / ReLU bits into ``out`` / ``bits`` (block-output prologue, PRO 3):
+    writes the output rows / ReLU bits into ``out`` / ``bits`` (block-output prologue, Src2.BLOCK_OUT):
     the separate apply pass and conv1's re-read of the output are gone."""
 
     __slots__ = ("out_ref", "z3", "cf3", "res", "cfd", "out", "bits")
@@ -209,37 +215,32 @@ class _Deferred:
             self.bits.copy_(b)
 
 
-def _resp_enabled(c: int) -> bool:
+def _resp_enabled() -> bool:
     """Block outputs are applied in the consumer's conv1 prologue (which consumers take it:
     models/resnet.py ResNet.forward, resp_consumer_ok) unless PS_AMD_DISABLE=block_out."""
     return knobs.enabled("block_out")
 
 
-def twosrc_glds_min_nk() -> int:
-    """Mirror of csrc convgemm.hip kTwosrcGldsMinNk: two-source prologues with K >= 64 x this run
-    on the LDS-DMA variant."""
-    return 4
-
-
-def big_tile(m: int, n: int, k: int, src2: int = 0, epi: int = 1, pro: bool = False) -> bool:
+def big_tile(m: int, n: int, k: int, src2: int = Src2.NONE, epi: int = Epi.STATS, pro: bool = False) -> bool:
     """Whether conv_gemm runs this 1x1 stride-1 GEMM ([m, k] x [k, n]) on the 256 x 256 tiles of
-    csrc/kernels/conv_big.hip (src2: 1 the block-output prologue, 2 the BN-backward prologue):
+    csrc/kernels/conv_big.hip (src2: ``Src2``; epi: ``Epi``; plain ints do too):
     there a prologue stages and transforms the A rows once per 256-channel tile, and the tiles of
     one pixel tile share an XCD, so the re-read that limits the 128-wide tiles to N <= 128 is gone."""
-    return tuple(native().conv_gemm_plan(m, n, k, [m, 1, m, 1, 1, 1, 0], pro, epi, src2)[:2]) == (256, 256)
+    return tuple(native().conv_gemm_plan(m, n, k, [m, 1, m, 1, 1, 1, 0], pro, int(epi), int(src2))[:2]) == (256, 256)
 
 
 def resp_consumer_ok(blk: nn.Module, m: int = 0) -> bool:
     """Whether the block-output prologue pays on ``blk``'s conv1: with one channel tile (N <= 128,
-    _twosrc_max_n) -- the layer-1 and layer-2 blocks and the layer-1 -> 2 boundary (LDS-DMA
+    TWOSRC_MAX_N) -- the layer-1 and layer-2 blocks and the layer-1 -> 2 boundary (LDS-DMA
     variant: 1.01 vs 1.21 ms at 256 -> 64 channels, 0.53 vs 0.62 ms at 512 -> 128); with two or
     more tiles each re-reads both sources and the apply pass + plain GEMM is faster
     (profiles/r4_twosrc_probe.txt)."""
     c1 = blk.conv1
-    if m > 0 and big_tile(m, c1.out_channels, c1.in_channels, src2=1):  # m: the consumer's input pixels
+    if m > 0 and big_tile(m, c1.out_channels, c1.in_channels, src2=Src2.BLOCK_OUT):  # m: the consumer's input pixels
         return True
-    return c1.out_channels <= _twosrc_max_n() and (
-        c1.in_channels >= 64 * twosrc_glds_min_nk() or c1.out_channels <= 64)
+    # (two-source prologues with K >= 64 x kTwosrcGldsMinNk run on the LDS-DMA variant)
+    return c1.out_channels <= TWOSRC_MAX_N and (
+        c1.in_channels >= 64 * native().kTwosrcGldsMinNk or c1.out_channels <= 64)
 
 
 def flush_deferred() -> None:
@@ -250,28 +251,14 @@ def flush_deferred() -> None:
         pend.flush()
 
 
-def _twosrc_max_n() -> int:
-    """Two-source prologues pay while the GEMM has ONE channel tile (N <= 128): every further tile
-    re-reads both row sources (scripts/probe_twosrc.py, profiles/r4_twosrc_probe.txt: conv3 data
-    grad 0.51 vs 0.64 ms at N = 128, 0.36 vs 0.25 ms at N = 512)."""
-    return 128
-
-
-def _bwd_prologue_enabled(c3: int, n: int = 0) -> bool:
+def _bwd_prologue_enabled(n: int) -> bool:
     """bn3 backward applied in the conv3 data-gradient prologue (one channel tile).  At 256 channels (4 K-stages, persistent
     grid) the prologue stages A through registers from TWO row sources and replaces the apply
     pass + the LDS-DMA GEMM (1.29 -> 1.05-1.08 ms per layer-1 block); deeper K (512-2048
     channels, where the register-staged GEMM was 2-6x slower: profiles/r3_bn_bwd_prologue_ab.txt)
     runs the LDS-DMA two-source variant: both row sources land in LDS by DMA and one in-place pass
     per stage applies the BN backward (csrc convgemm.hip TWO_GLDS, scripts/probe_twosrc.py)."""
-    return n <= _twosrc_max_n()
-
-
-def _pro_fuse_max_k() -> int:
-    """conv3's forward applies bn2 + ReLU while staging up to this many input channels; deeper
-    (layer 4, 512) the apply pass + plain GEMM is faster: 0.16 vs 0.21 ms (layer 3: 0.26 either
-    way; profiles/r4_twosrc_probe.txt, bn_relu_prologue rows)."""
-    return 256
+    return n <= TWOSRC_MAX_N
 
 
 def _conv3_bwd_fused(ci: int, co: int) -> bool:
@@ -296,8 +283,23 @@ def _fold_enabled() -> bool:
 
 
 def _fold_ds_enabled() -> bool:
-    """Downsample BN's backward reduce in the consumer block's conv1 data-gradient epilogue (9)."""
+    """Downsample BN's backward reduce in the consumer block's conv1 data-gradient epilogue
+    (Epi.FOLD_ADD_MASKED_DS)."""
     return knobs.enabled("fold_bn_ds")
+
+
+def _conv1_dgrad_epi(downsample: bool, stride: int, fold: bool, producer_ds: bool) -> Epi:
+    """Epilogue of conv1's data gradient: it adds the other branch's gradient -- the downsample
+    data gradient (stride 2: at the even pixels) or the identity gradient masked by the output
+    bits -- and, with ``fold``, reduces the producer block's bn3 backward (``producer_ds``: and
+    its downsample BN's sum)."""
+    if downsample:
+        if stride == 2:
+            return Epi.FOLD_ADD_S2 if fold else Epi.ADD_S2
+        return Epi.FOLD_ADD if fold else Epi.ADD
+    if not fold:
+        return Epi.ADD_MASKED
+    return Epi.FOLD_ADD_MASKED_DS if producer_ds else Epi.FOLD_ADD_MASKED
 
 
 class _BottleneckFn(torch.autograd.Function):
@@ -314,38 +316,39 @@ class _BottleneckFn(torch.autograd.Function):
         # kernel reads channel c's shift before it updates that channel's running mean
         k1 = bn1.running_mean
         if pend_in is not None:  # the previous block's output is applied (and stored) while staging
-            z1, p1 = nat.conv_gemm(pend_in.z3, _mat(w1), gi, pend_in.cf3, 1, None, k1, a2=pend_in.res,
-                                   pro2=pend_in.cfd, aout=x2, abits=pend_in.bits)
+            z1, p1 = nat.conv_gemm(pend_in.z3, _mat(w1), gi, pro=pend_in.cf3, epi=Epi.STATS, kshift=k1,
+                                   a2=pend_in.res, pro2=pend_in.cfd, aout=x2, abits=pend_in.bits)
             FOLD_STATS["resp"] += 1
         else:
-            z1, p1 = nat.conv_gemm(x2, _mat(w1), gi, None, 1, None, k1)
+            z1, p1 = nat.conv_gemm(x2, _mat(w1), gi, epi=Epi.STATS, kshift=k1)
         m1, i1, cf1 = _finalize(p1, k1, n * h * w, bn1)
         y1 = nat.bn_apply_coef(z1, cf1, None, None, 1)[0]
         if _conv3x3_enabled():
             # our implicit GEMM (LDS-DMA staging at this depth) with bn2's statistics in the epilogue
             k2 = bn2.running_mean
-            z2r, p2s = nat.conv_gemm(y1, _mat3(w2), geo(h, w, 3, s, 1), None, 1, None, k2)
+            z2r, p2s = nat.conv_gemm(y1, _mat3(w2), geo(h, w, 3, s, 1), epi=Epi.STATS, kshift=k2)
             m2, i2, cf2 = _finalize(p2s, k2, n * oh * ow, bn2)
         else:
             z2r = rows(F.conv2d(image(y1, n, h, w), w2, None, s, 1))
             m2, i2, cf2 = nat.bn_stats(z2r, g2, b2, bn2.running_mean, bn2.running_var, True, _momentum(bn2),
                                        float(bn2.eps))
         k3 = bn3.running_mean
-        if z2r.shape[1] <= _pro_fuse_max_k():
-            z3, p3 = nat.conv_gemm(z2r, _mat(w3), go, cf2, 1, None, k3)  # bn2 + ReLU in the prologue
+        if z2r.shape[1] <= PRO_FUSE_MAX_K:
+            z3, p3 = nat.conv_gemm(z2r, _mat(w3), go, pro=cf2, epi=Epi.STATS, kshift=k3)  # bn2 + ReLU in the prologue
         else:  # the apply pass + plain LDS-DMA GEMM is faster at this depth
-            z3, p3 = nat.conv_gemm(nat.bn_apply_coef(z2r, cf2, None, None, 1)[0], _mat(w3), go, None, 1, None, k3)
+            z3, p3 = nat.conv_gemm(nat.bn_apply_coef(z2r, cf2, None, None, 1)[0], _mat(w3), go, epi=Epi.STATS,
+                                   kshift=k3)
         m3, i3, cf3 = _finalize(p3, k3, n * oh * ow, bn3)
         cfd = None
         if wd is not None:
             bnd = blk.downsample[1]
             kd = bnd.running_mean
-            zd, pd = nat.conv_gemm(x2, _mat(wd), geo(h, w, 1, s), None, 1, None, kd)
+            zd, pd = nat.conv_gemm(x2, _mat(wd), geo(h, w, 1, s), epi=Epi.STATS, kshift=kd)
             md, idd, cfd = _finalize(pd, kd, n * oh * ow, bnd)
         else:
             zd = md = idd = None
         if (getattr(blk, "_defer_out", False) and getattr(_tls, "pending", None) is not None
-                and _resp_enabled(z3.shape[1])):
+                and _resp_enabled()):
             # the next fused block applies this output in its conv1 prologue and fills out / obits
             # (handed over through the thread-local, which also works under no_grad)
             out = torch.empty_like(z3)
@@ -378,7 +381,7 @@ class _BottleneckFn(torch.autograd.Function):
         w3t = pw[1] if pw else _mat(w3).t()
         lk = ctx.link_out
         dz3 = dw3f = None
-        ds_part = None  # [2, G, C] downsample-BN sums from the consumer's epilogue 9
+        ds_part = None  # [2, G, C] downsample-BN sums from the consumer's Epi.FOLD_ADD_MASKED_DS
         if (lk is not None and lk.part is not None and d2.data_ptr() == lk.dx_ptr
                 and d2._version == lk.dx_version):
             # the consumer block already masked dout and reduced bn3's backward sums
@@ -386,8 +389,8 @@ class _BottleneckFn(torch.autograd.Function):
                 ds_part = lk.part[0::2]  # sum(g), sum(g * xhat_d): a strided view, no copy
                 lk.part = lk.part[:2]
                 FOLD_STATS["ds"] += 1
-            if (_bwd_prologue_enabled(z3.shape[1], w3.shape[1])
-                    or big_tile(d2.shape[0], w3.shape[1], z3.shape[1], src2=2, epi=3)):
+            if (_bwd_prologue_enabled(w3.shape[1])
+                    or big_tile(d2.shape[0], w3.shape[1], z3.shape[1], src2=Src2.BN_BWD, epi=Epi.MASK_SUMS)):
                 # bn3's backward runs in the conv3 data-grad prologue, which also stores dz3 for
                 # the weight gradient: no separate apply pass over the widest tensors
                 dg3, db3, cb3 = nat.bn_bwd_coef(lk.part, g3, m3, i3, d2.shape[0])
@@ -396,7 +399,8 @@ class _BottleneckFn(torch.autograd.Function):
                     gy2, p2, dw3f = nat.conv11_bwd_fused(d2, z3, cb3, w3t.contiguous(), z2r, cf2, m2, i2)
                     FOLD_STATS["conv3_fused"] = FOLD_STATS.get("conv3_fused", 0) + 1
                 else:
-                    gy2, p2, dz3 = nat.conv_gemm(d2, w3t, go, None, 3, z2r, None, cf2, m2, i2, a2=z3, bwd=cb3)
+                    gy2, p2, dz3 = nat.conv_gemm(d2, w3t, go, epi=Epi.MASK_SUMS, aux=z2r, mc=cf2, mean=m2, invstd=i2,
+                                                 a2=z3, bwd=cb3)
             else:
                 dz3, dg3, db3 = nat.bn_bwd_partials(d2, z3, lk.part, g3, m3, i3)
                 gy2 = None
@@ -416,15 +420,16 @@ class _BottleneckFn(torch.autograd.Function):
             sd.fork()
             dw3 = sd.run(lambda: nat.conv_wgrad(dz3, z2r, go, cf2), dz3, z2r, cf2, like=w3)
         if gy2 is None:
-            gy2, p2 = nat.conv_gemm(dz3, w3t, go, None, 3, z2r, None, cf2, m2, i2)
+            gy2, p2 = nat.conv_gemm(dz3, w3t, go, epi=Epi.MASK_SUMS, aux=z2r, mc=cf2, mean=m2, invstd=i2)
         dz2, dg2, db2 = nat.bn_bwd_partials(gy2, z2r, p2, g2, m2, i2)
         c1, c2 = w2.shape[1], w2.shape[0]
         ours_dgrad = _conv3x3_enabled() and (s == 1 or (s == 2 and h % 2 == 0 and w % 2 == 0
-                                                         and w2.shape[1] >= _dgrad_s2_min_c()))
+                                                         and w2.shape[1] >= DGRAD_S2_MIN_C))
         # weight grad on the wide-tile kernel from 256 input channels up (on par with / faster than
         # MIOpen there: profiles/r2_wgrad_probe.jsonl), on the patch kernel at 64 / 128 channels
         # (csrc conv_wgrad_patch_kernel: 2.4x / 1.6x MIOpen, profiles/r3_wgrad_probe_patch.jsonl)
-        ours_wgrad = _conv3x3_enabled() and (c1 >= WGRAD3X3_MIN_C or _patch_wgrad_ok(h, w, c1, c2, s))
+        ours_wgrad = _conv3x3_enabled() and (c1 >= WGRAD3X3_MIN_C
+                                             or nat.conv_wgrad_patch_ok(geo(h, w, 3, s, 1), n, c2, c1))
         dy1 = dw2 = None
         sd.fork()
         if ours_wgrad:
@@ -442,17 +447,17 @@ class _BottleneckFn(torch.autograd.Function):
             # data grad = the forward GEMM over dz2 with the flipped, transposed weight; its epilogue
             # applies bn1's ReLU mask and reduces bn1's backward sums (no separate reduce pass)
             if s == 1:
-                gy1, p1b = nat.conv_gemm(dz2, pw[2] if pw else _mat3_dgrad(w2), geo(oh, ow, 3, 1, 1), None, 3, z1,
-                                         None, cf1, m1, i1)
+                gy1, p1b = nat.conv_gemm(dz2, pw[2] if pw else _mat3_dgrad(w2), geo(oh, ow, 3, 1, 1),
+                                         epi=Epi.MASK_SUMS, aux=z1, mc=cf1, mean=m1, invstd=i1)
             else:  # four stride-1 phase GEMMs, each writing every other dx row (no zero fill)
-                gy1, p1b = nat.conv_dgrad_s2(dz2, pw[2] if pw else _phase_weights(w2), h, w, 3, z1, cf1, m1, i1)
+                gy1, p1b = nat.conv_dgrad_s2(dz2, pw[2] if pw else _phase_weights(w2), h, w, epi=Epi.MASK_SUMS, z=z1,
+                                             mc=cf1, mean=m1, invstd=i1)
         li = ctx.link_in
         fold = li is not None and _fold_enabled()
         fkw = dict(mean=li.mean, invstd=li.invstd, aux2=li.z3, bits2=li.bits) if fold else {}
-        if wd is not None:
-            e1 = (8 if s == 2 else 7) if fold else (4 if s == 2 else 2)
-        else:
-            e1 = (9 if li.zd is not None else 6) if fold else 5
+        e1 = _conv1_dgrad_epi(wd is not None, s, fold, fold and li.zd is not None)
+        if e1 == Epi.FOLD_ADD_MASKED_DS:  # the producer has a downsample BN: its sum rides along
+            fkw.update(aux3=li.zd, mean2=li.md, invstd2=li.idd)
         # (bn1's backward as the conv1 data-gradient prologue on the 256 x 256 tiles cost more than
         # the apply pass it removes at K = 256 / 512 in the round-5 A/B, scripts/probe_conv_big.py; removed)
         if ours_dgrad:
@@ -480,13 +485,10 @@ class _BottleneckFn(torch.autograd.Function):
                     dzd, _, dgd, dbd = nat.bn_act_bwd(d2, None, zd, gd, md, idd, 3, False, True, None, obits)
                 sd.fork()
                 dwd = sd.run(lambda: nat.conv_wgrad(dzd, x2, geo(h, w, 1, s)), dzd, x2, like=wd)
-                t = nat.conv_gemm(dzd, wdt, go)[0]
-            r1 = nat.conv_gemm(a1, w1t, gi, None, e1, t, **fkw)
-        elif e1 == 9:  # the producer has a downsample BN: its sum rides along
-            r1 = nat.conv_gemm(a1, w1t, gi, None, 9, d2, bits=obits, aux3=li.zd, mean2=li.md, invstd2=li.idd,
-                               **fkw)
+                t = nat.conv_gemm(dzd, wdt, go, epi=Epi.STORE)[0]
+            r1 = nat.conv_gemm(a1, w1t, gi, epi=e1, aux=t, **fkw)
         else:
-            r1 = nat.conv_gemm(a1, w1t, gi, None, e1, d2, bits=obits, **fkw)
+            r1 = nat.conv_gemm(a1, w1t, gi, epi=e1, aux=d2, bits=obits, **fkw)
         dx2, part = r1[0], r1[1]
         if fold:
             # dx_keep pins a second reference on dx2's storage, so autograd cannot sum another
