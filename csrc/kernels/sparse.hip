@@ -159,7 +159,8 @@ __global__ __launch_bounds__(256) void segment_reduce_rows_kernel(const S* __res
   const int64_t nwaves = (static_cast<int64_t>(gridDim.x) * blockDim.x) >> 6;
   for (int64_t u = wave; u < nseg; u += nwaves) {
     const int64_t b = seg_off[u], e = seg_off[u + 1];
-    const float inv = mean ? 1.f / static_cast<float>(e - b) : 1.f;
+    // an empty segment divides by 1, as in the vectorised kernel (1 / 0 * 0 would store NaN)
+    const float inv = mean ? 1.f / static_cast<float>(e - b > 0 ? e - b : 1) : 1.f;
     for (int c = lane; c < dim; c += 64) {
       float acc = 0.f;
       for (int64_t j = b; j < e; ++j) acc += Elem<S>::load(src + perm[j] * dim, c);
@@ -326,6 +327,17 @@ __device__ __forceinline__ int vec_lanes_log2_dev(int dim) {  // lanes per row: 
   return __builtin_ctz(l);
 }
 
+// lo + span * u with the product and the sum rounded separately, as the host oracles compute it
+// (ops/sparse.py init_values, runtime/ps_server.cpp).  The build contracts a * b + c into one fma
+// (-ffp-contract=fast; the backend fuses whatever the source says, __fmul_rn / __fadd_rn and a
+// contract(off) pragma included), and the fma differs from the oracles in the last place unless
+// span is a power of two.  The empty asm makes the rounded product opaque, so it cannot be fused.
+__device__ __forceinline__ float init_value(float lo, float span, float u) {
+  float p = span * u;
+  asm volatile("" : "+v"(p));
+  return lo + p;
+}
+
 // rows: owner-local indices (negative = unresolved, skipped).  The RNG is keyed by the row's
 // GLOBAL key -- keys[r] when given (hash-mapped tables: the raw id), else row + row_base (range
 // partitioned tables: the global row) -- so a row's initial value does not depend on which rank
@@ -365,11 +377,13 @@ __global__ __launch_bounds__(256) void lazy_init_rows_kernel(float* __restrict__
         uint32_t rnd[4];
         Philox::gen(seed, static_cast<uint64_t>(q), rnd, grow);
         float* dst = table + rr * dim + q * 4;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = init_value(lo, span, Philox::u01(rnd[k]));
         if (q * 4 + 4 <= dim && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
-          store4(dst, 0, f32x4{lo + span * Philox::u01(rnd[0]), lo + span * Philox::u01(rnd[1]),
-                               lo + span * Philox::u01(rnd[2]), lo + span * Philox::u01(rnd[3])});
+          store4(dst, 0, f32x4{v[0], v[1], v[2], v[3]});
         } else {
-          for (int k = 0; k < 4 && q * 4 + k < dim; ++k) dst[k] = lo + span * Philox::u01(rnd[k]);
+          for (int k = 0; k < 4 && q * 4 + k < dim; ++k) dst[k] = v[k];
         }
       }
     }

@@ -80,6 +80,8 @@ def test_sparse_opt(kind, rowwise):
     ops.sparse_opt(kind, gt, g0, g1, rows.to(DEV), grad.to(DEV), rowwise=rowwise, skip_zero=skip, **hp)
     torch.testing.assert_close(gt.cpu(), rt, rtol=2e-5, atol=2e-5)
     torch.testing.assert_close(g0.cpu(), r0, rtol=2e-5, atol=2e-5)
+    if st1 is not None:  # Adam's v, FTRL's n
+        torch.testing.assert_close(g1.cpu(), r1, rtol=2e-5, atol=2e-5)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
