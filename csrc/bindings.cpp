@@ -382,6 +382,63 @@ void hash_slots(Tensor hkeys, Tensor ids, Tensor out, bool insert, Tensor status
                            out.data_ptr<int64_t>(), insert, status.data_ptr<int32_t>(), cur_stream(ids));
 }
 
+// Grow a map-mode shard on the device: every key of old_hkeys is re-inserted into new_hkeys
+// (pre-filled with -1, power-of-two capacity >= 2x the old one) and its table row, flag and
+// state entries move to the new slot.  states are [cap, dim] or row-wise [cap].  remap [old cap]
+// receives the new slot of each old position (-1 = empty).
+void rehash_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor new_table, Tensor old_flags,
+                 Tensor new_flags, std::vector<Tensor> old_states, std::vector<Tensor> new_states, Tensor remap) {
+  check_i64(old_hkeys, "old_hkeys");
+  check_i64(new_hkeys, "new_hkeys");
+  check_i64(remap, "remap");
+  check_f32(old_table, "old_table");
+  check_f32(new_table, "new_table");
+  check_gpu(old_flags, "old_flags");
+  check_gpu(new_flags, "new_flags");
+  const int64_t oc = old_hkeys.numel(), nc = new_hkeys.numel();
+  TORCH_CHECK(nc > 0 && (nc & (nc - 1)) == 0, "hash capacity must be a power of two");
+  TORCH_CHECK(nc >= 2 * oc, "rehash_rows: the new map must be at least twice the old one");
+  TORCH_CHECK(old_table.dim() == 2 && new_table.dim() == 2 && old_table.size(0) == oc && new_table.size(0) == nc &&
+                  old_table.size(1) == new_table.size(1) && old_table.size(1) >= 1,
+              "rehash_rows: tables [cap, dim]");
+  TORCH_CHECK(old_flags.scalar_type() == torch::kUInt8 && new_flags.scalar_type() == torch::kUInt8 &&
+                  old_flags.numel() == oc && new_flags.numel() == nc,
+              "rehash_rows: flags uint8 [cap]");
+  TORCH_CHECK(remap.numel() == oc, "rehash_rows: remap [old cap]");
+  for (const Tensor* t : {&new_hkeys, &old_table, &new_table, &old_flags, &new_flags, &remap})
+    TORCH_CHECK(t->device() == old_hkeys.device(), "rehash_rows: one device");
+  TORCH_CHECK(old_states.size() == new_states.size() && old_states.size() <= size_t(psamd::kRehashMaxState),
+              "rehash_rows: state lists");
+  psamd::RehashArgs a{};
+  a.old_hkeys = old_hkeys.data_ptr<int64_t>();
+  a.old_cap = oc;
+  a.new_hkeys = new_hkeys.data_ptr<int64_t>();
+  a.new_cap = nc;
+  a.old_table = old_table.data_ptr<float>();
+  a.new_table = new_table.data_ptr<float>();
+  a.dim = static_cast<int>(old_table.size(1));
+  a.old_flags = old_flags.data_ptr<uint8_t>();
+  a.new_flags = new_flags.data_ptr<uint8_t>();
+  a.nstate = static_cast<int>(old_states.size());
+  for (int i = 0; i < a.nstate; ++i) {
+    check_f32(old_states[i], "old state");
+    check_f32(new_states[i], "new state");
+    const bool full = old_states[i].dim() == 2;
+    TORCH_CHECK(old_states[i].device() == old_hkeys.device() && new_states[i].device() == old_hkeys.device(),
+                "rehash_rows: one device");
+    TORCH_CHECK(old_states[i].dim() == new_states[i].dim() && old_states[i].size(0) == oc &&
+                    new_states[i].size(0) == nc && old_states[i].numel() == oc * (full ? a.dim : 1) &&
+                    new_states[i].numel() == nc * (full ? a.dim : 1),
+                "rehash_rows: a state is [cap, dim] or [cap]");
+    a.old_st[i] = old_states[i].data_ptr<float>();
+    a.new_st[i] = new_states[i].data_ptr<float>();
+    a.st_full[i] = full ? 1 : 0;
+  }
+  a.remap = remap.data_ptr<int64_t>();
+  const c10::DeviceGuard guard(old_hkeys.device());
+  psamd::launch_rehash_rows(a, cur_stream(old_hkeys));
+}
+
 // ------------------------------------------------------------------------------ fused FC layer
 // dy, y [M, N]; x [M, K]; w [N, K]; all fp32 or all bf16, contiguous; outputs optional
 void fc_bwd(Tensor dy, Tensor y, Tensor x, Tensor w, c10::optional<Tensor> dw, c10::optional<Tensor> db,
@@ -1839,6 +1896,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lazy_init_rows", &lazy_init_rows, py::arg("table"), py::arg("rows"), py::arg("flags"), py::arg("seed"),
         py::arg("row_base"), py::arg("lo"), py::arg("hi"), py::arg("keys") = py::none());
   m.def("hash_slots", &hash_slots);
+  m.def("rehash_rows", &rehash_rows);
   m.def("unique_runs", &unique_runs);
   m.def("softmax_temp_fwd", &softmax_temp_fwd);
   m.def("softmax_temp_bwd", &softmax_temp_bwd);

@@ -152,6 +152,28 @@ void launch_unique_runs(const int64_t* srt, const int64_t* uidx, int64_t n, int6
                         int64_t* seg, hipStream_t s);
 void launch_hash_slots(int64_t* hkeys, int64_t capacity, const int64_t* ids, int64_t n, int64_t* out, int insert,
                        int32_t* status, hipStream_t s);
+// rehash of a map-mode shard into a larger one (keys, rows, flags, up to kRehashMaxState optimizer
+// states: st_full[i] = 1 for [cap, dim], 0 for row-wise [cap]); new_* pre-filled (-1 keys, zeros);
+// remap[old_cap] receives the new slot of every old position (-1 = was empty).  lg is the launcher's.
+constexpr int kRehashMaxState = 4;
+struct RehashArgs {
+  const int64_t* old_hkeys;
+  int64_t old_cap;
+  int64_t* new_hkeys;
+  int64_t new_cap;  // power of two
+  const float* old_table;
+  float* new_table;
+  int dim;
+  const uint8_t* old_flags;
+  uint8_t* new_flags;
+  const float* old_st[kRehashMaxState];
+  float* new_st[kRehashMaxState];
+  int st_full[kRehashMaxState];
+  int nstate;
+  int64_t* remap;
+  int lg;
+};
+void launch_rehash_rows(const RehashArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- fc.hip
 // fused FC backward: dW = (act'(y) * dy)^T x (+ db = column sums), dX = (act'(y) * dy) W;

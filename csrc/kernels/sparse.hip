@@ -21,6 +21,8 @@
 //                       (store/KVStore.java:86-107, net/PServer.java:143-162)
 //  hash_slots           device-resident id -> slot map (open addressing, CAS insert) for
 //                       tables keyed by unbounded ids; no host round trip per lookup
+//  rehash_rows          growth of such a map: one pass re-inserts every key into a larger map and
+//                       moves its row, flag and optimizer states to the new slot
 #include <algorithm>
 
 #include "psamd_device.h"
@@ -453,6 +455,92 @@ void launch_hash_slots(int64_t* hkeys, int64_t capacity, const int64_t* ids, int
   const int grid = stream_grid(n, 256);
   hipLaunchKernelGGL(hash_slots_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<unsigned long long*>(hkeys),
                      capacity - 1, ids, n, out, insert, status);
+}
+
+// Growth of a map-mode shard: ONE pass over the old map re-inserts every live key into a larger,
+// empty key array (same mix_key / linear probing as hash_slots_kernel) and moves its payload --
+// table row, init flag, optimizer states -- to the new probe position.  A wave takes 64 old
+// positions at a time.  First every lane inserts the key of one position (keys are unique, so a
+// CAS on an empty position wins or moves on) and moves its per-row scalars: 64 independent probe
+// chains per wave hide the latency of the dependent key load -> probe -> CAS.  Then groups of
+// 2^lg lanes own one position each: the new slot comes from the inserting lane by a wave
+// broadcast and the group copies the row, in 16-B pieces when VEC.  remap[p] = new slot of old
+// position p (-1 where p was empty) lets the host side translate slots it handed out before the
+// growth.  Every live row is read once and written once; destinations come zero-filled, so
+// untouched positions keep their meaning.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rehash_rows_kernel(const RehashArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane >> a.lg;
+  const int sl = lane & ((1 << a.lg) - 1);
+  const int gl = 1 << a.lg;
+  const int per_wave = 64 >> a.lg;
+  const int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = (static_cast<int64_t>(gridDim.x) * blockDim.x) >> 6;
+  const uint64_t mask = static_cast<uint64_t>(a.new_cap - 1);
+  const unsigned long long kEmpty = ~0ull;
+  unsigned long long* nk = reinterpret_cast<unsigned long long*>(a.new_hkeys);
+  for (int64_t base = wave * 64; base < a.old_cap; base += nwaves * 64) {  // wave-uniform
+    const int64_t pl = base + lane;
+    long long ql = -1;
+    if (pl < a.old_cap) {
+      const int64_t k = a.old_hkeys[pl];
+      if (k >= 0) {
+        const unsigned long long key = static_cast<unsigned long long>(k);
+        uint64_t h = mix_key(key) & mask;
+        for (int64_t probe = 0; probe < a.new_cap; ++probe) {
+          const unsigned long long cur = __hip_atomic_load(&nk[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (cur == kEmpty && atomicCAS(&nk[h], kEmpty, key) == kEmpty) { ql = static_cast<long long>(h); break; }
+          h = (h + 1) & mask;
+        }
+        if (ql >= 0) {
+          a.new_flags[ql] = a.old_flags[pl];
+          for (int s = 0; s < a.nstate; ++s)
+            if (!a.st_full[s]) a.new_st[s][ql] = a.old_st[s][pl];
+        }
+      }
+      a.remap[pl] = ql;
+    }
+    for (int j = 0; j < 64; j += per_wave) {
+      const long long q = __shfl(ql, j + sub, kWave);  // every lane of the wave gets here
+      if (q >= 0) {  // live position base + j + sub (< old_cap, or its lane would hold -1)
+        const int64_t so = (base + j + sub) * a.dim, dq = static_cast<int64_t>(q) * a.dim;
+        if (VEC) {
+          for (int c = sl * 4; c < a.dim; c += gl * 4) {
+            store4(a.new_table, dq + c, load4(a.old_table, so + c));
+            for (int s = 0; s < a.nstate; ++s)
+              if (a.st_full[s]) store4(a.new_st[s], dq + c, load4(a.old_st[s], so + c));
+          }
+        } else {
+          for (int c = sl; c < a.dim; c += gl) {
+            a.new_table[dq + c] = a.old_table[so + c];
+            for (int s = 0; s < a.nstate; ++s)
+              if (a.st_full[s]) a.new_st[s][dq + c] = a.old_st[s][so + c];
+          }
+        }
+      }
+    }
+  }
+}
+
+void launch_rehash_rows(const RehashArgs& a0, hipStream_t s) {
+  if (a0.old_cap <= 0) return;
+  RehashArgs a = a0;
+  bool vec = a.dim % 4 == 0 &&
+             ((reinterpret_cast<uintptr_t>(a.old_table) | reinterpret_cast<uintptr_t>(a.new_table)) & 15) == 0;
+  for (int i = 0; i < a.nstate; ++i)
+    if (a.st_full[i])
+      vec = vec && ((reinterpret_cast<uintptr_t>(a.old_st[i]) | reinterpret_cast<uintptr_t>(a.new_st[i])) & 15) == 0;
+  const int units = vec ? a.dim / 4 : a.dim;  // pieces per row: one per lane of the group, up to 16
+  a.lg = 0;
+  while ((1 << a.lg) < units && a.lg < 4) ++a.lg;
+  // one lane per position would be a one-shot grid: half of that, so every wave takes 64
+  // positions at least twice and the inserts of one batch overlap the row traffic of another
+  const int grid = stream_grid((a.old_cap + 1) / 2, 256);
+  if (vec)
+    hipLaunchKernelGGL(rehash_rows_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(rehash_rows_kernel<false>, dim3(grid), dim3(256), 0, s, a);
 }
 
 // Compaction of sorted keys: for every run head i (i == 0 or srt[i] != srt[i-1]) with unique

@@ -69,11 +69,14 @@ def connect(cfg: Config, device=None):
         if cons in ("asp", "ssp"):  # rows reached one-sidedly, no lockstep all-to-alls
             from ..parallel.async_rows import async_table_factory
 
+            if cfg.grow_rows:
+                raise ValueError("grow_rows needs consistency=bsp: async row tables have a fixed capacity")
+
             return tp, async_table_factory(tp, device, seed=cfg.seed,
                                            staleness=None if cons == "asp" else int(cfg.staleness))
         return tp, sharded_table_factory(tp, device, seed=cfg.seed, overlap=device is not None and
-                                         torch.device(device).type == "cuda")
-    return None, local_table_factory(device, seed=cfg.seed)
+                                         torch.device(device).type == "cuda", grow=cfg.grow_rows)
+    return None, local_table_factory(device, seed=cfg.seed, grow=cfg.grow_rows)
 
 
 def make_trainer(cfg: Config, model, device=None, conn=None) -> Trainer:

@@ -87,6 +87,7 @@ class Config:
     seed: int = 1234
     fault: str = ""  # e.g. "kill:rank=1:step=5", "delay_push:ms=50", "drop_push:p=0.01"
     heartbeat_s: float = 0.0
+    grow_rows: bool = False  # map-mode sparse tables enlarge themselves (standalone / bsp ranks)
 
     # ----------------------------------------------------------------- derived
     @property

@@ -37,24 +37,28 @@ from . import layers as L
 from .losses import CrossEntropy, Loss, SoftmaxLoss
 
 
-def local_table_factory(device=None, seed: int = 0, id_mode: str = "map"):
-    """Standalone tables (one process holds every row)."""
+def local_table_factory(device=None, seed: int = 0, id_mode: str = "map", grow: bool = False):
+    """Standalone tables (one process holds every row).  ``grow``: map-mode tables enlarge
+    themselves when ``rows`` turns out too small (tables of another mode are fixed-size)."""
     def make(name, dim, rows, init, mode=None, fields=1):
-        return SparseTable(name, dim, rows, init=init, id_mode=mode or id_mode, seed=stable_seed(name, seed),
-                           device=device, fields=fields)
+        m = mode or id_mode
+        return SparseTable(name, dim, rows, init=init, id_mode=m, seed=stable_seed(name, seed),
+                           device=device, fields=fields, grow=grow and m == "map")
 
     return make
 
 
 def sharded_table_factory(transport, device=None, seed: int = 0, id_mode: str = "map", overlap: bool = True,
-                          exchange=None):
+                          exchange=None, grow: bool = False):
     """Rows partitioned over the co-located servers of ``transport`` (torchrun ranks); with
     ``overlap`` (GPU) row gradients are pushed from backward hooks on a side stream.
-    ``exchange``: "plane" | "collective" | None (auto, see row_plane.plane_rows_wanted)."""
+    ``exchange``: "plane" | "collective" | None (auto, see row_plane.plane_rows_wanted).
+    ``grow``: map-mode tables enlarge their shards on demand (collective exchange only)."""
     def make(name, dim, rows, init, mode=None, fields=1):
-        return ShardedSparseTable(name, dim, rows, transport, init=init, id_mode=mode or id_mode,
+        m = mode or id_mode
+        return ShardedSparseTable(name, dim, rows, transport, init=init, id_mode=m,
                                   seed=stable_seed(name, seed), device=device, fields=fields, overlap=overlap,
-                                  exchange=exchange)
+                                  exchange=exchange, grow=grow and m == "map")
 
     return make
 

@@ -164,6 +164,81 @@ def hash_slots(hkeys: torch.Tensor, ids: torch.Tensor, insert: bool, status: tor
     return out
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix_key(x: int) -> int:
+    """``mix_key`` of csrc/kernels/sparse.hip on a Python int (the map's probe start)."""
+    x &= _M64
+    x ^= x >> 33
+    x = (x * 0xFF51AFD7ED558CCD) & _M64
+    x ^= x >> 33
+    x = (x * 0xC4CEB9FE1A85EC53) & _M64
+    return x ^ (x >> 33)
+
+
+def _probe_insert_cpu(new_hkeys: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """Host model of the device map's insertion (linear probing from ``mix_key``): slots of the
+    unique ``keys`` in the CPU array ``new_hkeys``, -1 for pad keys (< 0)."""
+    cap = new_hkeys.numel()
+    hk = new_hkeys.tolist()
+    pos = {k: i for i, k in enumerate(hk) if k >= 0}
+    out = []
+    for k in keys.tolist():
+        if k < 0:
+            out.append(-1)
+            continue
+        h = pos.get(k)
+        if h is None:
+            h = _mix_key(k) & (cap - 1)
+            for _ in range(cap):
+                if hk[h] < 0:
+                    break
+                h = (h + 1) & (cap - 1)
+            else:
+                h = -1
+            if h >= 0:
+                hk[h] = k
+                pos[k] = h
+        out.append(h)
+    new_hkeys.copy_(torch.tensor(hk, dtype=torch.int64))
+    return torch.tensor(out, dtype=torch.int64)
+
+
+def rehash_rows_ref(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_states, new_states):
+    """Oracle of ``rehash_rows`` as a composition: insert every old key into the new map
+    (``hash_slots`` on the GPU -- the empty entries are pad keys -1 and resolve to slot -1 -- or
+    the host model of the same probing on CPU tensors), then masked index copies."""
+    if old_hkeys.is_cuda:
+        status = torch.zeros(1, dtype=torch.int32, device=old_hkeys.device)
+        remap = hash_slots(new_hkeys, old_hkeys, True, status)
+    else:
+        remap = _probe_insert_cpu(new_hkeys, old_hkeys)
+    src = torch.nonzero(remap >= 0).reshape(-1)
+    dst = remap[src]
+    new_table[dst] = old_table[src]
+    new_flags[dst] = old_flags[src]
+    for o, n in zip(old_states, new_states):
+        n[dst] = o[src]
+    return remap
+
+
+def rehash_rows(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_states=(), new_states=()):
+    """Move a map-mode shard into a larger one in one pass (HIP on the GPU): every key of
+    ``old_hkeys`` is inserted into ``new_hkeys`` (power-of-two capacity >= 2x, pre-filled with -1)
+    and its table row, flag and state entries ([cap, dim] or row-wise [cap]) move to the new slot.
+    The ``new_*`` tensors come zero-filled.  -> remap [old cap]: new slot of every old position,
+    -1 where it was empty."""
+    if new_hkeys.numel() < 2 * old_hkeys.numel():
+        raise ValueError("rehash_rows: the new map must be at least twice the old one")
+    if use_native(old_table, old_hkeys):
+        remap = torch.empty_like(old_hkeys)
+        native().rehash_rows(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, list(old_states),
+                             list(new_states), remap)
+        return remap
+    return rehash_rows_ref(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_states, new_states)
+
+
 class _GatherUnique(torch.autograd.Function):
     """out[k] = leaf[inv[k]] (cast to out_dtype); backward = deterministic segment sum of the
     output gradient per unique row (sorted-order perm + seg_off), no atomics, no sort."""

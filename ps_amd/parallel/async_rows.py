@@ -99,7 +99,11 @@ class AsyncRowTable(TcpSparseTable):
     def __init__(self, name: str, dim: int, rows: Union[int, Sequence[int]], transport: Transport,
                  updater: Optional[Updater] = None, *, init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "map",
                  seed: int = 0, fields: int = 1, device=None, staleness: Optional[int] = None,
-                 capacity: int = 1 << 15, rows_per_owner: Optional[int] = None, timeout_s: float = 600.0):
+                 capacity: int = 1 << 15, rows_per_owner: Optional[int] = None, timeout_s: float = 600.0,
+                 grow: bool = False):
+        if grow:  # the native owner thread holds raw pointers into the shard (set_shard)
+            raise ValueError("AsyncRowTable does not support grow=True: its owner thread serves the shard's "
+                             "tensors in place; size it with rows_per_owner (growable tables need bsp)")
         self.t = transport
         self.W, self.me = transport.world, transport.rank
         super().__init__(name, dim, rows, _AsyncRowClient(self), updater, init=init, id_mode=id_mode, seed=seed,

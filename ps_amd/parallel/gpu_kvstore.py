@@ -297,9 +297,11 @@ class GpuKVStore:
 
     # ------------------------------------------------------------------ sparse rows
     def add_table(self, name: str, dim: int, rows: Union[int, Sequence[int]], updater: Optional[Updater] = None, *,
-                  init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "map", seed: int = 0, fields: int = 1):
+                  init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "map", seed: int = 0, fields: int = 1,
+                  grow: bool = False):
         """A row-sparse table on the same ranks (collective).  Rows are created lazily on first
-        pull with a deterministic init keyed by the global row key."""
+        pull with a deterministic init keyed by the global row key.  ``grow`` (bsp, map mode):
+        the owners enlarge their shards when ``rows`` turns out too small."""
         if name in self.tables:
             raise KeyError(f"table {name!r} exists")
         from .sparse_table import stable_seed
@@ -308,13 +310,13 @@ class GpuKVStore:
             from .sparse_table import ShardedSparseTable
 
             tab = ShardedSparseTable(name, dim, rows, self.t, updater, init=init, id_mode=id_mode,
-                                     seed=stable_seed(name, seed), device=self.device, fields=fields)
+                                     seed=stable_seed(name, seed), device=self.device, fields=fields, grow=grow)
         else:
             from .async_rows import AsyncRowTable
 
             tab = AsyncRowTable(name, dim, rows, self.t, updater, init=init, id_mode=id_mode,
                                 seed=stable_seed(name, seed), device=self.device, fields=fields,
-                                staleness=None if self.consistency == "asp" else self.staleness)
+                                staleness=None if self.consistency == "asp" else self.staleness, grow=grow)
         self.tables[name] = tab
         return tab
 

@@ -34,6 +34,13 @@ exchange instead of one getList per field:
   (slot, grad) pairs and applies once at the end of the round -- one optimizer step per row
   per round, the reference Trainer's single KVStore.update (train/Trainer.java:93).
 
+* growth   (map mode, ``grow=True``) the reference's server map has no size limit
+  (store/KVStore.java:86-107); here ``rows`` sizes the shard, and a growable owner enlarges it
+  before its device map would pass load 1/2: one HIP pass (``rehash_rows``) moves keys, rows,
+  flags and optimizer states into fresh tensors, and the slots of pushes still in flight are
+  translated.  ``GrowthPolicy`` decides from host bookkeeping and asynchronous live counts, so
+  steady state stays host-sync-free.  W = 1 and the collective exchange; not the row plane.
+
 ``SparseTable`` is the W = 1 (standalone) table.  The TCP-server equivalent for the
 dedicated-server topology is ``TcpSparseTable`` (rows live in the native server's row tables).
 """
@@ -123,12 +130,78 @@ class _HostIdMap:
         return self._m.size() if self._m is not None else len(self._d)
 
 
+# Load factors of a growable device map (live keys / capacity).  Linear probing is designed for
+# at most GROW_HARD_LOAD; a growth re-sizes for GROW_TARGET_LOAD; above GROW_SOFT_LOAD the exact
+# live count is refreshed in the background so that the next decision needs no wait.
+GROW_HARD_LOAD = (1, 2)
+GROW_SOFT_LOAD = (3, 8)
+GROW_TARGET_LOAD = (1, 4)
+
+
+class GrowthPolicy:
+    """When a growable device map is enlarged -- bookkeeping only, no device calls.
+
+    The exact live-key count is known only at snapshots (a device count copied to the host
+    asynchronously); between them ``since`` counts every key looked up with insert (pads and
+    duplicates included), so ``bound = live_snap + since`` never underestimates the load.
+    The owner of the map drives it: ``admit(n, poll, wait)`` before a lookup of ``n`` keys with
+    insert -> the capacity to grow to, or None; ``launched(n)`` after it -> True when a snapshot
+    should be enqueued now (stream order makes it include that lookup's inserts).  ``poll()``
+    returns the count of the snapshot in flight if it has landed, else None; ``wait()`` blocks
+    for it.  At most one snapshot is in flight."""
+
+    def __init__(self, cap: int, live: int = 0):
+        self.cap, self.live_snap, self.since = int(cap), int(live), 0
+        self.in_flight = False
+        self._mark = 0  # ``since`` when the snapshot in flight was enqueued
+        self.waits = 0
+        self.grows = 0
+
+    @property
+    def bound(self) -> int:
+        return self.live_snap + self.since
+
+    def _over(self, n: int, load: Tuple[int, int]) -> bool:
+        return (self.bound + n) * load[1] > self.cap * load[0]
+
+    def _fold(self, live: int) -> None:
+        self.live_snap = int(live)
+        self.since -= self._mark
+        self._mark = 0
+        self.in_flight = False
+
+    def admit(self, n: int, poll: Optional[Callable] = None, wait: Optional[Callable] = None) -> Optional[int]:
+        if self.in_flight:
+            v = poll()
+            if v is not None:
+                self._fold(v)
+        if self._over(n, GROW_HARD_LOAD) and self.in_flight:  # only the exact count can still say no
+            self.waits += 1
+            self._fold(wait())
+        if not self._over(n, GROW_HARD_LOAD):
+            return None
+        self.cap = _pow2((self.bound + n) * GROW_TARGET_LOAD[1] // GROW_TARGET_LOAD[0])
+        self.grows += 1
+        return self.cap
+
+    def launched(self, n: int) -> bool:
+        self.since += int(n)
+        if self.in_flight or not self._over(0, GROW_SOFT_LOAD):
+            return False
+        self.in_flight = True
+        self._mark = self.since
+        return True
+
+
 class RowShard:
     """Owner-side storage of one table shard: fp32 rows, init flags, optimizer state, and
-    (map mode) the key -> slot map -- a device hash map on the GPU, the native IdMap on CPU."""
+    (map mode) the key -> slot map -- a device hash map on the GPU, the native IdMap on CPU.
+    With ``grow`` (map mode) the shard enlarges itself instead of running full: ``on_grow(remap)``
+    is called after every growth (``remap``: old slot -> new slot on the GPU, None on the CPU,
+    where slots are insertion-ordered and stay)."""
 
     def __init__(self, dim: int, capacity: int, mode: str, row_base: int, seed: int, init: Tuple[float, float],
-                 device, updater: Optional[Updater]):
+                 device, updater: Optional[Updater], grow: bool = False):
         self.dim, self.mode, self.row_base, self.seed = int(dim), mode, int(row_base), int(seed)
         self.init = init
         self.device = device
@@ -143,6 +216,13 @@ class RowShard:
         else:
             self.hkeys = self.idmap = None
         self.capacity = int(capacity)
+        if grow and mode != "map":
+            raise ValueError("grow=True needs id_mode='map'")
+        self.growable = bool(grow)
+        self.on_grow: Optional[Callable] = None
+        self.stats = {"host_syncs": 0}  # the owning table shares its own dict
+        self._pol = GrowthPolicy(self.capacity) if self.growable and self.gpu else None
+        self._snap: Optional[Tuple[torch.Tensor, object]] = None  # (pinned count, event) in flight
         self.status = torch.zeros(1, dtype=torch.int32, device=device)  # map miss / overflow flag
         self.table = torch.zeros(self.capacity, self.dim, dtype=torch.float32, device=device)
         self.flags = torch.zeros(self.capacity, dtype=torch.uint8, device=device)
@@ -162,11 +242,82 @@ class RowShard:
         if self.mode != "map":
             return keys - self.row_base
         if self.gpu:
-            return _sp.hash_slots(self.hkeys, keys, insert, self.status)
+            if not (insert and self.growable):
+                return _sp.hash_slots(self.hkeys, keys, insert, self.status)
+            n = keys.numel()
+            new_cap = self._pol.admit(n, self._snap_poll, self._snap_wait)
+            if new_cap is not None:
+                self.grow(new_cap)
+            out = _sp.hash_slots(self.hkeys, keys, True, self.status)
+            if self._pol.launched(n):
+                self._snap_enqueue()
+            return out
+        if insert and self.growable and len(self.idmap) + keys.numel() > self.capacity:
+            self.grow(max(2 * self.capacity, len(self.idmap) + keys.numel()))
         s = self.idmap.lookup(keys, insert).to(keys.device)
         if insert and bool((s < 0).any()):
             raise RuntimeError(f"sparse table shard full ({self.capacity} rows)")
         return s
+
+    # ---- growth (map mode): the live-count snapshot is the pattern of ShardedSparseTable._route
+    def _snap_enqueue(self) -> None:
+        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+        host.copy_((self.hkeys != -1).sum().reshape(1), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._snap = (host, ev)
+
+    def _snap_poll(self) -> Optional[int]:
+        host, ev = self._snap
+        if not ev.query():
+            return None
+        self._snap = None
+        return int(host[0])
+
+    def _snap_wait(self) -> int:
+        host, ev = self._snap
+        self.stats["host_syncs"] += 1
+        ev.synchronize()
+        self._snap = None
+        return int(host[0])
+
+    def _zeros_like_cap(self, t: torch.Tensor, cap: int) -> torch.Tensor:
+        return torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+
+    def grow(self, new_cap: int) -> Optional[torch.Tensor]:
+        """Enlarge the shard to ``new_cap`` slots, keeping every row, flag and optimizer state.
+        GPU: one ``rehash_rows`` pass on the current stream into fresh tensors (the slot of a key
+        is its probe position, so slots move) -> remap [old capacity].  CPU: the tensors are
+        extended with zeros and the id map rebuilt; slots stay -> None.  A local decision of this
+        owner: no collective."""
+        if self.mode != "map":
+            raise RuntimeError("only map-mode shards grow")
+        new_cap = int(new_cap)
+        remap = None
+        if self.gpu:
+            new_cap = _pow2(new_cap)
+            if new_cap < 2 * self.capacity:
+                raise ValueError(f"grow: {new_cap} slots is less than twice the current {self.capacity}")
+            hkeys = torch.full((new_cap,), -1, dtype=torch.int64, device=self.device)
+            table = self._zeros_like_cap(self.table, new_cap)
+            flags = self._zeros_like_cap(self.flags, new_cap)
+            states = [self._zeros_like_cap(s, new_cap) for s in self.states]
+            remap = _sp.rehash_rows(self.hkeys, hkeys, self.table, table, self.flags, flags, self.states, states)
+            self.hkeys, self.table, self.flags, self.states = hkeys, table, flags, states
+            if self._pol is not None:
+                self._pol.cap = new_cap
+        else:
+            if new_cap <= self.capacity:
+                raise ValueError(f"grow: {new_cap} rows is not more than the current {self.capacity}")
+            pairs = self.idmap.items()
+            self.idmap = type(self.idmap)(new_cap)
+            self.idmap.restore(pairs)
+            ext = lambda t: torch.cat([t, self._zeros_like_cap(t, new_cap - self.capacity)])  # noqa: E731
+            self.table, self.flags, self.states = ext(self.table), ext(self.flags), [ext(s) for s in self.states]
+        self.capacity = new_cap
+        if self.on_grow is not None:
+            self.on_grow(remap)
+        return remap
 
     def read(self, slots: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
         """Rows at ``slots`` (lazy deterministic init of untouched rows, RNG keyed by ``keys``)."""
@@ -204,6 +355,8 @@ class RowShard:
         return d
 
     def load_state_dict(self, d: dict) -> None:
+        if self.growable and int(d["table"].shape[0]) != self.capacity:
+            self._adopt_capacity(d)
         self.table.copy_(d["table"])
         self.flags.copy_(d["flags"])
         for s, src in zip(self.states, d["states"]):
@@ -212,6 +365,23 @@ class RowShard:
             self.hkeys.copy_(d["hkeys"])
         if self.idmap is not None and "idmap" in d:
             self.idmap.restore(d["idmap"])
+        if self._pol is not None and "hkeys" in d:  # exact count from the saved map, nothing in flight
+            self._pol = GrowthPolicy(self.capacity, live=int((d["hkeys"] != -1).sum()))
+            self._snap = None
+
+    def _adopt_capacity(self, d: dict) -> None:
+        """A growable shard resumes a checkpoint of any capacity: reallocate to the saved shapes."""
+        cap = int(d["table"].shape[0])
+        if len(d["states"]) != len(self.states):
+            raise ValueError("sparse-table checkpoint was written with a different optimizer")
+        self.table = self._zeros_like_cap(self.table, cap)
+        self.flags = self._zeros_like_cap(self.flags, cap)
+        self.states = [self._zeros_like_cap(s, cap) for s in self.states]
+        if self.hkeys is not None:
+            self.hkeys = torch.full((cap,), -1, dtype=torch.int64, device=self.device)
+        if self.idmap is not None:
+            self.idmap = type(self.idmap)(cap)
+        self.capacity = cap
 
 
 @dataclass
@@ -255,14 +425,22 @@ class ShardedSparseTable:
     """Rows partitioned over the co-located servers of ``transport`` (W = 1 without one).
 
     ``rows``: rows per field (int, or one int per field).  ``fields`` > 1 makes lookups take
-    ids of shape [..., fields] (one table for all fields of a layer)."""
+    ids of shape [..., fields] (one table for all fields of a layer).  ``grow`` (map mode): the
+    shard enlarges itself when ``rows`` turns out too small (``stats["grows"]`` /
+    ``stats["capacity"]``); at W > 1 such tables use the collective exchange."""
 
     def __init__(self, name: str, dim: int, rows: Union[int, Sequence[int]], transport: Optional[Transport] = None,
                  updater: Optional[Updater] = None, *, init: Tuple[float, float] = (0.0, 0.0),
                  id_mode: str = "direct", seed: int = 0, device=None, fields: int = 1, overlap: bool = False,
-                 average: bool = True, exchange: Optional[str] = None):
+                 average: bool = True, exchange: Optional[str] = None, grow: bool = False):
         if id_mode not in ("direct", "hash", "map"):
             raise ValueError(id_mode)
+        if grow and id_mode != "map":
+            raise ValueError(f"grow=True needs id_mode='map' (got {id_mode!r}): other modes index rows directly")
+        if grow and exchange == "plane":
+            raise ValueError("grow=True is not supported with exchange='plane': the row plane's accumulator is "
+                             "sized by the shard; use the collective exchange")
+        self.growable = bool(grow)
         self.t = transport or Transport()
         self.world, self.rank = self.t.world, self.t.rank
         self.name, self.dim, self.id_mode = name, int(dim), id_mode
@@ -284,7 +462,7 @@ class ShardedSparseTable:
         self.per_rank = (self.rows + self.world - 1) // self.world
         if id_mode == "map":
             cap = self.rows if self.world == 1 else int(self.per_rank * 1.25) + 64
-            self.shard = RowShard(dim, cap, "map", 0, seed, init, self.device, updater)
+            self.shard = RowShard(dim, cap, "map", 0, seed, init, self.device, updater, grow=self.growable)
         else:
             self.shard = RowShard(dim, self.per_rank, "direct", self.rank * self.per_rank, seed, init, self.device,
                                   updater)
@@ -296,7 +474,10 @@ class ShardedSparseTable:
         self._pending: List[_Plan] = []
         self._acc: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self._push_done: Optional[torch.cuda.Event] = None
-        self.stats = {"pulls": 0, "pushes": 0, "rows_pulled": 0, "rows_pushed": 0, "host_syncs": 0}
+        self.stats = {"pulls": 0, "pushes": 0, "rows_pulled": 0, "rows_pushed": 0, "host_syncs": 0, "grows": 0,
+                      "capacity": self.shard.capacity}
+        self.shard.stats = self.stats  # waits for a live-count snapshot count as host syncs
+        self.shard.on_grow = self._on_grow
         self._pf: dict = {}  # ids signature -> (keys, route) of prefetched lookups
         self._nbad: Optional[torch.Tensor] = None  # deferred out-of-range id count (sync-free path)
         self._rows_dev = torch.zeros((), dtype=torch.int64, device=self.device)  # sync-free rows pulled
@@ -310,7 +491,9 @@ class ShardedSparseTable:
 
             if exchange not in (None, "auto", "plane", "collective"):
                 raise ValueError(exchange)
-            if _rp.plane_rows_wanted(self.t, self.device, exchange):
+            if self.growable:  # every rank alike, so skipping the plane's probe is collective-safe
+                self.exchange_info["fallback"] = "growable table: the row plane does not migrate its accumulator"
+            elif _rp.plane_rows_wanted(self.t, self.device, exchange):
                 from .remote_probe import RemoteWriteUnavailable
 
                 try:
@@ -385,6 +568,26 @@ class ShardedSparseTable:
         if self._push_done is not None:
             torch.cuda.current_stream(self.device).wait_event(self._push_done)
             self._push_done = None
+
+    def _on_grow(self, remap: Optional[torch.Tensor]) -> None:
+        """The shard grew (inside ``slots``, i.e. after ``_wait_push``: ordered behind every earlier
+        update).  On the GPU slots moved: translate every owner-local slot still to be used --
+        the unpushed plans (in place: hook closures hold the plan) and the queued micro-batches."""
+        self.stats["grows"] += 1
+        self.stats["capacity"] = self.shard.capacity
+        if remap is None:
+            return
+
+        def move(s: torch.Tensor) -> torch.Tensor:  # a gather that keeps the pad slot -1
+            out = torch.where(s >= 0, remap[s.clamp(min=0)], s)
+            if self.overlap:  # consumed by the push on the side stream
+                out.record_stream(side_stream(self.device))
+            return out
+
+        for plan in self._pending:
+            if not plan.pushed and plan.rslots is not None:
+                plan.rslots = move(plan.rslots)
+        self._acc = [(move(sl), g) for sl, g in self._acc]
 
     def _route(self, keys: torch.Tensor, nbad: torch.Tensor) -> "_Route":
         """Device half of the routing: dedupe + owner sort, per-owner unique counts and the count
@@ -706,6 +909,7 @@ class ShardedSparseTable:
         if int(d.get("world", self.world)) != self.world:
             raise ValueError("sparse-table checkpoint was written with a different world size")
         self.shard.load_state_dict(d)
+        self.stats["capacity"] = self.shard.capacity
         self.round = int(d["round"])
 
 
@@ -714,9 +918,9 @@ class SparseTable(ShardedSparseTable):
 
     def __init__(self, name: str, dim: int, rows: Union[int, Sequence[int]], updater: Optional[Updater] = None, *,
                  init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "direct", seed: int = 0, device=None,
-                 fields: int = 1, overlap: bool = False):
+                 fields: int = 1, overlap: bool = False, grow: bool = False):
         super().__init__(name, dim, rows, None, updater, init=init, id_mode=id_mode, seed=seed, device=device,
-                         fields=fields, overlap=overlap)
+                         fields=fields, overlap=overlap, grow=grow)
 
 
 # ------------------------------------------------------------------------------ TCP rows
