@@ -1294,7 +1294,10 @@ std::vector<Tensor> bn_act_bwd(Tensor dy, c10::optional<Tensor> y, Tensor x, c10
   check_f32(mean, "mean");
   check_f32(invstd, "invstd");
   TORCH_CHECK(mean.numel() == C && invstd.numel() == C, "stats size");
-  if (gamma.has_value() && gamma->defined()) check_f32(*gamma, "gamma");
+  if (gamma.has_value() && gamma->defined()) {
+    check_f32(*gamma, "gamma");
+    TORCH_CHECK(gamma->numel() == C, "gamma size");
+  }
   const c10::DeviceGuard guard(x.device());
   auto fopt = x.options().dtype(torch::kFloat32);
   auto dx = torch::empty_like(x);

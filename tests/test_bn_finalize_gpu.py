@@ -1,6 +1,8 @@
-"""One-launch BN finalize (csrc/kernels/bn_act.hip bn_fin3_kernel) straight from producer partial sums
-[2, G, C]: the forward statistics (bn_finalize_sums) and the backward coefficients (bn_bwd_coef) vs
-an fp64 torch reference, at partial-row counts from 1 to past the chunk cap, bitwise repeatable."""
+"""BN finalize (csrc/kernels/bn_act.hip) straight from producer partial sums [2, G, C]: the forward
+statistics (bn_finalize_sums: bn_finalize_kernel with an explicit kshift) and the backward
+coefficients (bn_bwd_coef: bn_bwd_finalize_kernel), both behind partials_fold_kernel once G exceeds
+2 * kFoldRows, vs an fp64 torch reference, at partial-row counts from 1 to past the fold threshold
+and the fin_threads steps, bitwise repeatable."""
 import pytest
 import torch
 
