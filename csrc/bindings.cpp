@@ -299,6 +299,47 @@ void segment_reduce_rows(Tensor src, Tensor perm, Tensor seg_off, Tensor out, bo
                                     out.data_ptr(), dcode(out, "out"), mean, cur_stream(src));
 }
 
+// -> path taken (0 generic, 1 vector)
+int64_t bag_pool_fwd(Tensor rows, Tensor inv, Tensor bag_off, c10::optional<Tensor> w, Tensor out, bool mean) {
+  check_f32(rows, "rows");
+  check_i64(inv, "inv");
+  check_i64(bag_off, "bag_off");
+  check_gpu(out, "out");
+  TORCH_CHECK(rows.dim() == 2 && out.dim() == 2 && rows.size(1) == out.size(1), "rows/out [*, dim]");
+  TORCH_CHECK(bag_off.numel() == out.size(0) + 1, "bag_off must have nbags+1 entries");
+  if (w.has_value() && w->defined()) {
+    check_f32(*w, "w");
+    TORCH_CHECK(w->numel() == inv.numel(), "w must have one weight per value (nnz)");
+  }
+  const c10::DeviceGuard guard(rows.device());
+  return psamd::launch_bag_pool_fwd(rows.data_ptr<float>(), inv.data_ptr<int64_t>(), bag_off.data_ptr<int64_t>(),
+                                    opt_ptr<const float>(w), out.size(0), static_cast<int>(rows.size(1)),
+                                    out.data_ptr(), dcode(out, "out"), mean, cur_stream(rows));
+}
+
+int64_t bag_pool_bwd(Tensor dout, Tensor perm, Tensor seg_off, Tensor bag_of, Tensor bag_off,
+                     c10::optional<Tensor> w, Tensor drows, bool mean) {
+  check_gpu(dout, "dout");
+  check_i64(perm, "perm");
+  check_i64(seg_off, "seg_off");
+  check_i64(bag_of, "bag_of");
+  check_i64(bag_off, "bag_off");
+  check_f32(drows, "drows");
+  TORCH_CHECK(dout.dim() == 2 && drows.dim() == 2 && dout.size(1) == drows.size(1), "dout/drows [*, dim]");
+  TORCH_CHECK(seg_off.numel() == drows.size(0) + 1, "seg_off must have nseg+1 entries");
+  TORCH_CHECK(bag_off.numel() == dout.size(0) + 1, "bag_off must have nbags+1 entries");
+  TORCH_CHECK(perm.numel() == bag_of.numel(), "perm and bag_of must have one entry per value (nnz)");
+  if (w.has_value() && w->defined()) {
+    check_f32(*w, "w");
+    TORCH_CHECK(w->numel() == bag_of.numel(), "w must have one weight per value (nnz)");
+  }
+  const c10::DeviceGuard guard(dout.device());
+  return psamd::launch_bag_pool_bwd(dout.data_ptr(), dcode(dout, "dout"), perm.data_ptr<int64_t>(),
+                                    seg_off.data_ptr<int64_t>(), bag_of.data_ptr<int64_t>(),
+                                    bag_off.data_ptr<int64_t>(), opt_ptr<const float>(w), drows.size(0),
+                                    static_cast<int>(dout.size(1)), drows.data_ptr<float>(), mean, cur_stream(dout));
+}
+
 void scatter_add_rows(Tensor src, Tensor rows, Tensor table) {
   check_gpu(src, "src");
   check_i64(rows, "rows");
@@ -1893,6 +1934,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("onebit_unpack_reduce", &onebit_unpack_reduce);
   m.def("gather_rows", &gather_rows);
   m.def("segment_reduce_rows", &segment_reduce_rows);
+  m.def("bag_pool_fwd", &bag_pool_fwd);
+  m.def("bag_pool_bwd", &bag_pool_bwd);
   m.def("scatter_add_rows", &scatter_add_rows);
   m.def("embedding_bag_fwd", &embedding_bag_fwd);
   m.def("sparse_lr_fwd", &sparse_lr_fwd);

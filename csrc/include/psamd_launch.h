@@ -135,6 +135,14 @@ void launch_onebit_unpack_reduce(const uint64_t* words, const float* scales, int
                                  int64_t words_stride, int64_t scales_stride, void* out, int odtype, float mult,
                                  int accumulate, hipStream_t s);
 
+// ---------------------------------------------------------------- bags.hip
+// -> the path taken: 0 generic (one wave per bag / segment), 1 vector (2^lg lanes, 16-B loads)
+int launch_bag_pool_fwd(const float* rows, const int64_t* inv, const int64_t* bag_off, const float* w,
+                        int64_t nbags, int dim, void* out, int odtype, int mean, hipStream_t s);
+int launch_bag_pool_bwd(const void* dout, int ddtype, const int64_t* perm, const int64_t* seg_off,
+                        const int64_t* bag_of, const int64_t* bag_off, const float* w, int64_t nseg, int dim,
+                        float* drows, int mean, hipStream_t s);
+
 // ---------------------------------------------------------------- sparse.hip
 void launch_gather_rows(const void* table, int tdtype, const int64_t* rows, int64_t nrows, int dim, void* out,
                         int odtype, int64_t out_ld, int64_t out_off, int act, hipStream_t s);

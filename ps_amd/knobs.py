@@ -36,6 +36,8 @@ ROUTES: Dict[str, str] = {
     "fused_attn": "short-sequence attention on SDPA",
     "flash_attn": "causal GQA attention on SDPA",
     "fused_xent": "cross-entropy on fp32 logits through F.cross_entropy",
+    # sparse rows (ops/sparse.py)
+    "bag_pool": "multi-hot bags pooled by gather_rows -> weight multiply -> segment_reduce_rows ([nnz, dim] in HBM)",
 }
 
 _cache: Dict[str, FrozenSet[str]] = {}

@@ -61,6 +61,12 @@ class MultiTableEmbedding(SparseLayerMixin, nn.Module):
         """ids [B, T] (per-table row ids) -> [B, T, dim]."""
         return self._lookup(self.table, ids, self.out_dtype)
 
+    def forward_bags(self, values: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                     mode: str = "sum") -> torch.Tensor:
+        """Multi-hot input: values [nnz] (per-table row ids, bag-major), offsets [B*T + 1]; bag g is
+        (sample g // T, table g % T) -> [B, T, dim], each vector the pooled rows of its bag."""
+        return self._lookup_bags(self.table, values, offsets, weights, mode, self.out_dtype)
+
 
 class DLRM(nn.Module):
     def __init__(self, dense_in: int = 13, table_rows: Sequence[int] = (100000,) * 26, dim: int = 128,
@@ -77,19 +83,27 @@ class DLRM(nn.Module):
         self.register_buffer("iu0", iu[0], persistent=False)
         self.register_buffer("iu1", iu[1], persistent=False)
 
-    def forward(self, dense: torch.Tensor, sparse: torch.Tensor) -> torch.Tensor:
+    def forward(self, dense: torch.Tensor, sparse) -> torch.Tensor:
+        """``sparse``: ids [B, T] (one id per table), or a tuple (values, offsets[, weights]) of
+        multi-hot bags (``MultiTableEmbedding.forward_bags``), sum-pooled."""
         x = self.bottom(dense.to(self.bottom[0].weight.dtype))  # [B, dim]
         self.emb.out_dtype = x.dtype
-        e = self.emb(sparse)  # [B, T, dim] in the compute dtype (cast fused into the gather)
+        if isinstance(sparse, (tuple, list)):
+            e = self.emb.forward_bags(*sparse)  # [B, T, dim], pooled in the fused bag kernel
+        else:
+            e = self.emb(sparse)  # [B, T, dim] in the compute dtype (cast fused into the gather)
         # [x | triu(z z^T)], z = [x; e]: one fused MFMA kernel on GPU bf16 (ops/dense.py)
         return self.top(dlrm_interact(x, e)).squeeze(1)
 
     def push_sparse(self) -> int:
         return self.emb.push_sparse()
 
-    def prefetch(self, sparse: torch.Tensor) -> None:
+    def prefetch(self, sparse) -> None:
         """Route the next batch's ids ahead of time (no host wait on its lookup at W > 1)."""
-        self.emb.table.prefetch(sparse)
+        if isinstance(sparse, (tuple, list)):
+            self.emb.table.prefetch_bags(sparse[0], sparse[1])
+        else:
+            self.emb.table.prefetch(sparse)
 
     def pull_weights(self) -> None:
         self.emb.clear()
@@ -110,3 +124,24 @@ def dlrm_batch(batch: int, table_rows: Sequence[int], dense_in: int = 13, seed: 
     if device is not None:
         dense, sparse, y = dense.to(device), sparse.to(device), y.to(device)
     return dense, sparse, y
+
+
+def dlrm_batch_multihot(batch: int, table_rows: Sequence[int], max_hot: int, dense_in: int = 13, seed: int = 0,
+                        device=None, zipf: float = 1.05, min_hot: int = 0):
+    """Synthetic multi-hot batch: every (sample, table) bag holds min_hot..max_hot ids (uniform
+    length) drawn from the power law of ``dlrm_batch``.  -> dense, (values, offsets), y with values
+    [nnz] bag-major and offsets [batch * T + 1]."""
+    g = torch.Generator().manual_seed(seed)
+    T = len(table_rows)
+    dense = torch.log1p(torch.rand(batch, dense_in, generator=g) * 100)
+    lens = torch.randint(min_hot, max_hot + 1, (batch * T,), generator=g)
+    offsets = torch.zeros(batch * T + 1, dtype=torch.int64)
+    torch.cumsum(lens, 0, out=offsets[1:])
+    table_of = torch.repeat_interleave(torch.arange(batch * T) % T, lens)
+    r = torch.tensor(list(table_rows), dtype=torch.int64)[table_of]
+    u = torch.rand(table_of.numel(), generator=g)
+    values = torch.minimum((torch.pow(u, zipf * 3) * r).long().clamp_(min=0), r - 1)  # skewed towards small ids
+    y = (torch.rand(batch, generator=g) < 0.25).float()
+    if device is not None:
+        dense, values, offsets, y = dense.to(device), values.to(device), offsets.to(device), y.to(device)
+    return dense, (values, offsets), y

@@ -112,6 +112,14 @@ class SparseLayerMixin:
             used.append(table)
         return table.lookup(ids, out_dtype, grad_fn)
 
+    def _lookup_bags(self, table, values: torch.Tensor, offsets: torch.Tensor, weights=None, mode: str = "sum",
+                     out_dtype=None, grad_fn=None) -> torch.Tensor:
+        """pooled rows of the bags (values, offsets); autograd to the pulled rows of ``table``."""
+        used = self._tables_used()
+        if not any(t is table for t in used):
+            used.append(table)
+        return table.lookup_bags(values, offsets, weights=weights, mode=mode, out_dtype=out_dtype, grad_fn=grad_fn)
+
     def push_sparse(self) -> int:
         """Push gradients of the rows touched since the last call; returns rows pushed."""
         return sum(t.push_pending() for t in self._tables_used())
@@ -180,6 +188,34 @@ class EmbeddingLayer(SparseLayerMixin, nn.Module):
         else:
             e = self._lookup(self.tables[0], ids, None, gfn)  # [N, fields, dim]
         e = e.reshape(ids.shape[0], self.fields * self.dim)
+        return self.act(e) if self.act is not None else e
+
+
+class EmbeddingBagLayer(SparseLayerMixin, nn.Module):
+    """Multi-hot categorical fields: every (sample, field) holds a list of ids (a bag) and the
+    field's vector is the sum (``mode="mean"``: mean; with weights: weighted sum) of their rows;
+    outputs stacked into one [N, fields*dim] slice like ``EmbeddingLayer``.  The fields share ONE
+    table (``table.fields == fields``); the pooling is the fused HIP bag kernel on the GPU."""
+
+    def __init__(self, name: str, fields: int, dim: int, table, mode: str = "sum", activation: Optional[str] = None):
+        super().__init__()
+        if getattr(table, "fields", 1) != fields:
+            raise ValueError(f"table has {table.fields} fields, layer needs {fields}")
+        if mode not in ("sum", "mean"):
+            raise ValueError(mode)
+        self.lname, self.fields, self.dim, self.table, self.mode = name, fields, dim, table, mode
+        self.act_name = activation
+        self.act = A.get(activation)
+
+    @property
+    def output_dims(self):
+        return self.fields * self.dim
+
+    def forward(self, values: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor] = None):
+        """values [nnz] int64 bag-major, offsets [N*fields + 1] int64 (bag g = sample g // fields,
+        field g % fields), optional weights [nnz] -> [N, fields*dim]."""
+        e = self._lookup_bags(self.table, values, offsets, weights, self.mode)
+        e = e.reshape(-1, self.fields * self.dim)
         return self.act(e) if self.act is not None else e
 
 

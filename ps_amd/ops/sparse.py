@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import torch
 
+from .. import knobs
 from ._ext import native, use_native
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
@@ -50,6 +51,85 @@ def segment_reduce_rows(src: torch.Tensor, perm: torch.Tensor, seg_off: torch.Te
         acc /= cnt.clamp(min=1).float()[:, None]
     out.copy_(acc.to(out.dtype))
     return out
+
+
+def _bag_of(bag_off: torch.Tensor, nnz: int) -> torch.Tensor:
+    """Bag index of every value position, from the bag offsets alone (no host sync)."""
+    pos = torch.arange(nnz, dtype=torch.int64, device=bag_off.device)
+    return torch.searchsorted(bag_off[1:].contiguous(), pos, right=True)
+
+
+def _bag_scale(bag_off: torch.Tensor) -> torch.Tensor:
+    """1 / max(1, len) per bag, fp32 (mean mode)."""
+    return 1.0 / (bag_off[1:] - bag_off[:-1]).clamp(min=1).float()
+
+
+def bag_pool_fwd(rows: torch.Tensor, inv: torch.Tensor, bag_off: torch.Tensor, out: torch.Tensor,
+                 weights: torch.Tensor | None = None, mean: bool = False, return_path: bool = False):
+    """out[g] = s_g * sum_{j in [bag_off[g], bag_off[g+1])} weights[j] * rows[inv[j]], s_g = 1 / max(1, len_g)
+    in mean mode, else 1; an empty bag gives a zero row.  rows fp32 [nu, dim], out fp32 / bf16 [G, dim].
+
+    GPU: the fused HIP kernel (csrc/kernels/bags.hip); with the ``bag_pool`` route disabled the
+    composition of the one-hot kernels (gather_rows -> weight multiply -> segment_reduce_rows),
+    which writes the [nnz, dim] rows to memory.  CPU: torch ops.  ``return_path`` -> (out, path):
+    1 vector kernel, 0 generic kernel, -1 composition / CPU."""
+    path = -1
+    nnz = inv.numel()
+    if use_native(rows, inv):
+        if knobs.enabled("bag_pool"):
+            path = int(native().bag_pool_fwd(rows, inv, bag_off, weights, out, bool(mean)))
+        else:
+            src = torch.empty(nnz, rows.shape[1], dtype=torch.float32, device=rows.device)
+            native().gather_rows(rows, inv, src, 0, ACT_NONE)
+            if weights is not None:
+                src *= weights[:, None]
+            pos = torch.arange(nnz, dtype=torch.int64, device=rows.device)
+            native().segment_reduce_rows(src, pos, bag_off, out, bool(mean))
+    else:
+        src = rows[inv].float()
+        if weights is not None:
+            src = src * weights[:, None].float()
+        acc = torch.zeros(out.shape, dtype=torch.float32).index_add_(0, _bag_of(bag_off, nnz), src)
+        if mean:
+            acc *= _bag_scale(bag_off)[:, None]
+        out.copy_(acc.to(out.dtype))
+    return (out, path) if return_path else out
+
+
+def bag_pool_bwd(dout: torch.Tensor, perm: torch.Tensor, seg_off: torch.Tensor, bag_of: torch.Tensor,
+                 bag_off: torch.Tensor, drows: torch.Tensor, weights: torch.Tensor | None = None,
+                 mean: bool = False, return_path: bool = False):
+    """drows[u] = sum_{j in [seg_off[u], seg_off[u+1])} weights[p] * s_{g} * dout[g], p = perm[j],
+    g = bag_of[p]: the gradient of ``bag_pool_fwd`` w.r.t. the unique rows, summed per row in the
+    sorted order of the plan (deterministic; an empty segment gives zeros).  dout fp32 / bf16
+    [G, dim], drows fp32 [nseg, dim].  Paths as in ``bag_pool_fwd``."""
+    path = -1
+    if use_native(dout, perm):
+        if knobs.enabled("bag_pool"):
+            path = int(native().bag_pool_bwd(dout, perm, seg_off, bag_of, bag_off, weights, drows, bool(mean)))
+        else:
+            src = torch.empty(bag_of.numel(), dout.shape[1], dtype=torch.float32, device=dout.device)
+            native().gather_rows(dout, bag_of, src, 0, ACT_NONE)
+            scale = weights
+            if mean:
+                s = _bag_scale(bag_off)[bag_of]
+                scale = s if scale is None else scale * s
+            if scale is not None:
+                src *= scale[:, None]
+            native().segment_reduce_rows(src, perm, seg_off, drows, False)
+    else:
+        src = dout.float()[bag_of]
+        scale = None if weights is None else weights.float()
+        if mean:
+            s = _bag_scale(bag_off)[bag_of]
+            scale = s if scale is None else scale * s
+        if scale is not None:
+            src = src * scale[:, None]
+        cnt = seg_off[1:] - seg_off[:-1]
+        seg_ids = torch.repeat_interleave(torch.arange(cnt.numel()), cnt)
+        acc = torch.zeros(drows.shape, dtype=torch.float32).index_add_(0, seg_ids, src[perm])
+        drows.copy_(acc)
+    return (drows, path) if return_path else drows
 
 
 def dedup_rows(ids: torch.Tensor, grads: torch.Tensor, mean: bool = False, out_dtype=None):
@@ -280,3 +360,47 @@ def gather_unique(leaf: torch.Tensor, inv: torch.Tensor, perm: torch.Tensor, seg
     if use_native(leaf, inv):
         return _GatherUnique.apply(leaf, inv.reshape(-1), perm, seg_off, out_dtype)
     return leaf[inv.reshape(-1)].to(out_dtype)
+
+
+class _PoolUnique(torch.autograd.Function):
+    """out[g] = s_g * sum_{j in bag g} weights[j] * leaf[inv[j]] (cast to out_dtype); backward = the
+    deterministic per-unique-row sum of the scaled bag gradients (``bag_pool_bwd``).  Neither pass
+    writes an [nnz, dim] tensor unless the ``bag_pool`` route is disabled."""
+
+    @staticmethod
+    def forward(ctx, leaf, inv, perm, seg_off, bag_off, bag_of, weights, mean, out_dtype):
+        out = torch.empty(bag_off.numel() - 1, leaf.shape[1], dtype=out_dtype, device=leaf.device)
+        bag_pool_fwd(leaf, inv, bag_off, out, weights, mean)
+        ctx.save_for_backward(perm, seg_off, bag_off, bag_of, weights)
+        ctx.nrows, ctx.mean = leaf.shape[0], bool(mean)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        perm, seg_off, bag_off, bag_of, weights = ctx.saved_tensors
+        dleaf = torch.empty(ctx.nrows, dout.shape[1], dtype=torch.float32, device=dout.device)
+        bag_pool_bwd(dout.contiguous(), perm, seg_off, bag_of, bag_off, dleaf, weights, ctx.mean)
+        return dleaf, None, None, None, None, None, None, None, None
+
+
+def pool_unique(leaf: torch.Tensor, inv: torch.Tensor, perm: torch.Tensor, seg_off: torch.Tensor,
+                bag_off: torch.Tensor, bag_of: torch.Tensor, weights: torch.Tensor | None = None,
+                mean: bool = False, out_dtype=None) -> torch.Tensor:
+    """Pooled ``gather_unique``: bag g (value positions bag_off[g] .. bag_off[g+1], ``bag_of`` their
+    bag index) -> the sum (``mean``: the mean; ``weights``: the weighted sum) of leaf[inv[j]] over
+    its values, [G, dim].  GPU path = the HIP bag kernels, CPU = differentiable torch ops.
+    ``weights`` gets no gradient."""
+    if weights is not None and weights.requires_grad:
+        raise ValueError("pool_unique: weights get no gradient (detach them)")
+    out_dtype = out_dtype or leaf.dtype
+    inv = inv.reshape(-1)
+    if use_native(leaf, inv):
+        w = None if weights is None else weights.float().contiguous()
+        return _PoolUnique.apply(leaf, inv, perm, seg_off, bag_off, bag_of, w, bool(mean), out_dtype)
+    src = leaf[inv]
+    if weights is not None:
+        src = src * weights[:, None].to(src.dtype)
+    out = torch.zeros(bag_off.numel() - 1, leaf.shape[1], dtype=leaf.dtype).index_add(0, bag_of, src)
+    if mean:
+        out = out * _bag_scale(bag_off)[:, None]
+    return out.to(out_dtype)

@@ -41,6 +41,11 @@ exchange instead of one getList per field:
   translated.  ``GrowthPolicy`` decides from host bookkeeping and asynchronous live counts, so
   steady state stays host-sync-free.  W = 1 and the collective exchange; not the row plane.
 
+* bags     ``lookup_bags(values, offsets)``: a multi-hot field holds a list of ids and its vector is
+  the sum / mean / weighted sum of their rows.  Keys, plan, exchange, push and growth are those of
+  ``lookup``; between the pulled unique rows and the model the gather is replaced by the fused HIP
+  pooling (``ops.sparse.pool_unique``), so no [nnz, dim] tensor exists in either direction.
+
 ``SparseTable`` is the W = 1 (standalone) table.  The TCP-server equivalent for the
 dedicated-server topology is ``TcpSparseTable`` (rows live in the native server's row tables).
 """
@@ -545,7 +550,10 @@ class ShardedSparseTable:
             f = torch.arange(self.fields, device=self.device).expand_as(ids)
         else:
             f = torch.zeros_like(ids)
-        ids, f = ids.reshape(-1), f.reshape(-1)
+        return self._keys_flat(ids.reshape(-1), f.reshape(-1))
+
+    def _keys_flat(self, ids: torch.Tensor, f: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The key arithmetic of ``keys_of`` on flat int64 ids and their flat field indices."""
         if self.id_mode == "map":
             bad = (ids < 0) | (ids >= (1 << KEY_ID_BITS))
             keys = (f << KEY_ID_BITS) | ids.clamp(0, (1 << KEY_ID_BITS) - 1)
@@ -744,15 +752,83 @@ class ShardedSparseTable:
         else:
             keys, nbad = self.keys_of(ids)
             plan, rows = self._plan(keys, nbad)
+        leaf = self._leaf_of(plan, rows, grad_fn)
+        out = _sp.gather_unique(leaf, plan.inv, plan.perm, plan.seg_off, out_dtype)
+        return out.view(*ids.shape, self.dim)
+
+    def _leaf_of(self, plan: _Plan, rows: torch.Tensor, grad_fn: Optional[Callable]) -> torch.Tensor:
+        """The pulled rows as an autograd leaf whose gradient this plan pushes."""
         want_grad = torch.is_grad_enabled()
         leaf = rows.detach().requires_grad_(want_grad)
-        out = _sp.gather_unique(leaf, plan.inv, plan.perm, plan.seg_off, out_dtype)
         if want_grad:
             plan.leaf, plan.grad_fn = leaf, grad_fn
             self._pending.append(plan)
             if self.overlap:
                 leaf.register_post_accumulate_grad_hook(lambda _p, pl=plan: self._push_plan(pl, not self.accumulating))
-        return out.view(*ids.shape, self.dim)
+        return leaf
+
+    def _bag_keys(self, values: torch.Tensor, offsets: torch.Tensor):
+        """(values, offsets, bag_of, keys, #invalid ids) of a bag-major multi-hot input; host checks
+        cover what the host knows (shapes, G % fields), everything else stays on the device."""
+        if values.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError(f"{self.name}: values [nnz] and offsets [G + 1] must be 1-D")
+        G = offsets.numel() - 1
+        if G % self.fields:
+            raise ValueError(f"{self.name}: {G} bags is not a multiple of fields {self.fields}")
+        values = values.to(self.device).long().contiguous()
+        offsets = offsets.to(self.device).long().contiguous()
+        bag_of = _sp._bag_of(offsets, values.numel())
+        f = torch.remainder(bag_of, self.fields) if self.fields > 1 else torch.zeros_like(bag_of)
+        keys, nbad = self._keys_flat(values, f)
+        return values, offsets, bag_of, keys, nbad
+
+    def prefetch_bags(self, values: torch.Tensor, offsets: torch.Tensor) -> None:
+        """``prefetch`` for the next ``lookup_bags(values, offsets)`` (keyed on both tensors)."""
+        if (self.world == 1 and self.gpu) or self.plane is not None:
+            return  # no host-side sizes to wait for
+        _, _, _, keys, nbad = self._bag_keys(values, offsets)
+        if len(self._pf) >= 4:
+            self._pf.pop(next(iter(self._pf)))
+        self._pf[(self._ids_sig(values), self._ids_sig(offsets))] = (keys, self._route(keys, nbad))
+
+    def lookup_bags(self, values: torch.Tensor, offsets: torch.Tensor, *, weights: Optional[torch.Tensor] = None,
+                    mode: str = "sum", out_dtype=None, grad_fn: Optional[Callable] = None) -> torch.Tensor:
+        """Pooled multi-hot lookup -> [B, fields, dim] ([G, dim] when fields == 1).
+
+        ``values`` [nnz] int64 ids, bag-major; bag g is (sample g // fields, field g % fields) and
+        holds values[offsets[g] : offsets[g + 1]]; ``offsets`` [G + 1] int64 with offsets[0] == 0 and
+        offsets[-1] == nnz, G = B * fields.  A bag's vector is the sum of its rows (``mode="mean"``:
+        their mean; ``weights`` [nnz]: the weighted sum, no gradient to the weights); an empty bag
+        gives zeros, and nnz == 0 is legal.  The unique rows are pulled, exposed as a leaf and pushed
+        exactly as in ``lookup``; only the gather is replaced by the fused pooling
+        (``ops.sparse.pool_unique``), so no [nnz, dim] tensor is written in either direction.
+
+        Only shapes and G % fields are checked (they are host-known).  Offsets that are not
+        non-decreasing from 0 to nnz are the caller's contract, like ids in ``direct`` mode: they
+        are not validated and index out of bounds."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"{self.name}: mode {mode!r} (sum | mean)")
+        if weights is not None:
+            if weights.requires_grad:
+                raise ValueError(f"{self.name}: weights get no gradient (detach them)")
+            if weights.shape != values.shape:
+                raise ValueError(f"{self.name}: weights {tuple(weights.shape)} != values {tuple(values.shape)}")
+            weights = weights.to(self.device).float().contiguous()
+        pf = self._pf.pop((self._ids_sig(values), self._ids_sig(offsets)), None) if self._pf else None
+        values, offsets, bag_of, keys, nbad = self._bag_keys(values, offsets)
+        G = offsets.numel() - 1
+        shape = (G, self.dim) if self.fields == 1 else (G // self.fields, self.fields, self.dim)
+        if values.numel() == 0 and self.world == 1:  # nothing to pull or push
+            return torch.zeros(shape, dtype=out_dtype or torch.float32, device=self.device)
+        if pf is not None:
+            keys, route = pf
+            plan, rows = self._plan(keys, route.nbad, route=route)
+        else:
+            plan, rows = self._plan(keys, nbad)
+        leaf = self._leaf_of(plan, rows, grad_fn)
+        out = _sp.pool_unique(leaf, plan.inv, plan.perm, plan.seg_off, offsets, bag_of, weights, mode == "mean",
+                              out_dtype)
+        return out.view(shape)
 
     def pull_keys(self, keys: torch.Tensor) -> torch.Tensor:
         keys = keys.to(self.device).long().reshape(-1)
