@@ -113,6 +113,128 @@ void fused_opt(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::optional<
   psamd::launch_fused_opt(a, cur_stream(w));
 }
 
+// Test bindings of the owner-side "reduce + serve" kernels (fused_opt_multi_kernel, reduce_multi_kernel)
+// with caller-chosen off / nsrc / n; the plane (csrc/plane.cpp) fills its MultiGrad from IPC-mapped
+// buckets.  Everything the kernels would read or write out of bounds or misaligned is refused here.
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// -> g_bf16 of the sources (0 for the 1-bit form)
+int fill_multi(psamd::MultiGrad& m, const std::vector<Tensor>& srcs, int64_t off, int64_t n, const Tensor& seg,
+               const c10::optional<Tensor>& words, const c10::optional<Tensor>& scales) {
+  TORCH_CHECK(off >= 0, "off must be >= 0, got ", off);
+  TORCH_CHECK(n >= 0, "n must be >= 0, got ", n);
+  m = psamd::MultiGrad{};
+  m.off = off;
+  const bool onebit = words.has_value() && words->defined();
+  TORCH_CHECK(onebit == (scales.has_value() && scales->defined()), "words and scales come together");
+  if (onebit) {
+    TORCH_CHECK(srcs.empty(), "the 1-bit form takes no srcs");
+    check_i64(*words, "words");
+    check_f32(*scales, "scales");
+    TORCH_CHECK(words->dim() == 2 && scales->dim() == 2 && words->size(0) == scales->size(0),
+                "words [nsrc, nw] and scales [nsrc, ns]");
+    const int64_t nsrc = words->size(0), nw = words->size(1), ns = scales->size(1);
+    TORCH_CHECK(nsrc >= 1 && nsrc <= psamd::kPlaneMaxSrc, "1..", psamd::kPlaneMaxSrc, " sources, got ", nsrc);
+    TORCH_CHECK(words->device() == seg.device() && scales->device() == seg.device(), "words / scales device");
+    TORCH_CHECK(off + n <= 64 * nw, "off + n = ", off + n, " past the ", 64 * nw, " bits of words");
+    TORCH_CHECK(off + n <= psamd::kOnebitChunk * ns, "off + n = ", off + n, " past the ", ns, " chunk scales");
+    for (int64_t s = 0; s < nsrc; ++s) {
+      m.words[s] = reinterpret_cast<const uint64_t*>(words->data_ptr<int64_t>()) + s * nw;
+      m.scales[s] = scales->data_ptr<float>() + s * ns;
+    }
+    m.nsrc = static_cast<int>(nsrc);
+    m.onebit = 1;
+    return 0;
+  }
+  TORCH_CHECK(!srcs.empty() && srcs.size() <= static_cast<size_t>(psamd::kPlaneMaxSrc), "1..", psamd::kPlaneMaxSrc,
+              " sources, got ", srcs.size());
+  const int g_bf16 = dcode(srcs[0], "srcs[0]");
+  for (size_t s = 0; s < srcs.size(); ++s) {
+    check_gpu(srcs[s], "srcs[s]");
+    TORCH_CHECK(srcs[s].scalar_type() == srcs[0].scalar_type(), "sources of mixed dtypes");
+    TORCH_CHECK(srcs[s].device() == seg.device(), "sources of mixed devices");
+    TORCH_CHECK(off + n <= srcs[s].numel(), "off + n = ", off + n, " past source ", s, " of ", srcs[s].numel());
+    TORCH_CHECK(al16(srcs[s].data_ptr()), "source ", s, " is not 16-byte aligned");
+    m.g[s] = srcs[s].data_ptr();
+  }
+  m.nsrc = static_cast<int>(srcs.size());
+  m.onebit = 0;
+  return g_bf16;
+}
+
+// the phase contract of the multi kernels: element head = (8 - (off & 7)) & 7 of every array of the
+// segment is 16-byte aligned (the arrays are slices [off, off + n) of whole-chunk buffers)
+void check_phase(const Tensor& t, int64_t off, const char* name) {
+  const int64_t head = (8 - (off & 7)) & 7;
+  TORCH_CHECK(al16(static_cast<const char*>(t.data_ptr()) + head * t.element_size()), name,
+              " does not share the phase of off = ", off, ": element ", head, " is not 16-byte aligned");
+}
+
+void fused_opt_multi(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::optional<Tensor> st1,
+                     std::vector<Tensor> srcs, int64_t off, c10::optional<Tensor> wout, double lr, double beta1,
+                     double beta2, double eps, double wd, double momentum, double dampening, bool nesterov,
+                     bool adamw, double bc1, double bc2, double l1, double l2, double fbeta, int64_t ftrl_mode,
+                     double gscale, c10::optional<Tensor> gscale_t, c10::optional<Tensor> words,
+                     c10::optional<Tensor> scales) {
+  check_f32(w, "w");
+  const int64_t n = w.numel();
+  TORCH_CHECK(kind >= 0 && kind <= 3, "kind must be 0..3");
+  const bool has0 = st0.has_value() && st0->defined(), has1 = st1.has_value() && st1->defined();
+  for (const auto* st : {&st0, &st1}) {
+    if (!st->has_value() || !(*st)->defined()) continue;
+    check_f32(**st, "st0 / st1");
+    TORCH_CHECK((*st)->numel() == n && (*st)->device() == w.device(), "st0 / st1: w's size and device");
+  }
+  if (kind == 1 || kind == 3) TORCH_CHECK(has0 && has1, "adam/ftrl need 2 states");
+  if (kind == 2) TORCH_CHECK(has0, "adagrad needs a state");
+  if (kind == 0 && momentum != 0.0) TORCH_CHECK(has0, "momentum sgd needs a buffer");
+  int wout_bf16 = 0;
+  const bool haso = wout.has_value() && wout->defined();
+  if (haso) {
+    check_gpu(*wout, "wout");
+    TORCH_CHECK(wout->numel() == n && wout->device() == w.device(), "wout size / device");
+    wout_bf16 = dcode(*wout, "wout");
+  }
+  if (gscale_t.has_value() && gscale_t->defined()) {
+    check_f32(*gscale_t, "gscale_t");
+    TORCH_CHECK(gscale_t->numel() >= 1 && gscale_t->device() == w.device(), "gscale_t: float[1] on w's device");
+  }
+  psamd::MultiGrad m;
+  const int g_bf16 = fill_multi(m, srcs, off, n, w, words, scales);
+  check_phase(w, off, "w");
+  if (has0) check_phase(*st0, off, "st0");
+  if (has1) check_phase(*st1, off, "st1");
+  if (haso) check_phase(*wout, off, "wout");
+  const c10::DeviceGuard guard(w.device());
+  psamd::FusedOptArgs a;
+  a.kind = static_cast<int>(kind);
+  a.w = w.data_ptr<float>();
+  a.st0 = opt_ptr<float>(st0);
+  a.st1 = opt_ptr<float>(st1);
+  a.g = nullptr;
+  a.g_bf16 = g_bf16;
+  a.wout = opt_ptr<void>(wout);
+  a.wout_bf16 = wout_bf16;
+  a.n = n;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.momentum = momentum;
+  a.dampening = dampening; a.nesterov = nesterov; a.adamw = adamw; a.bc1 = bc1; a.bc2 = bc2;
+  a.l1 = l1; a.l2 = l2; a.fbeta = fbeta; a.ftrl_mode = static_cast<int>(ftrl_mode);
+  a.gscale = gscale;
+  a.gscale_ptr = opt_ptr<const float>(gscale_t);
+  psamd::launch_fused_opt_multi(a, m, cur_stream(w));
+}
+
+void reduce_multi(std::vector<Tensor> srcs, int64_t off, int64_t n, Tensor out, c10::optional<Tensor> words,
+                  c10::optional<Tensor> scales) {
+  check_f32(out, "out");
+  TORCH_CHECK(out.numel() == n, "out holds ", out.numel(), " elements, n = ", n);
+  psamd::MultiGrad m;
+  const int g_bf16 = fill_multi(m, srcs, off, n, out, words, scales);
+  check_phase(out, off, "out");
+  const c10::DeviceGuard guard(out.device());
+  psamd::launch_reduce_multi(m, g_bf16, n, out.data_ptr<float>(), cur_stream(out));
+}
+
 void sparse_opt(int64_t kind, Tensor table, c10::optional<Tensor> st0, c10::optional<Tensor> st1, Tensor rows,
                 Tensor grad, bool rowwise, bool skip_zero, double lr, double beta1, double beta2, double eps,
                 double wd, double momentum, double dampening, bool nesterov, bool adamw, double bc1, double bc2,
@@ -1917,6 +2039,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rcoef") = py::none(), py::arg("act") = 1, py::arg("want_mask") = false);
   m.def("bn_bwd_partials", &bn_bwd_partials);
   m.def("fused_opt", &fused_opt);
+  m.def("fused_opt_multi", &fused_opt_multi);
+  m.def("reduce_multi", &reduce_multi);
   m.def("sparse_opt", &sparse_opt, py::arg("kind"), py::arg("table"), py::arg("st0"), py::arg("st1"),
         py::arg("rows"), py::arg("grad"), py::arg("rowwise"), py::arg("skip_zero"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"),

@@ -52,6 +52,14 @@ HP_SETS = {
     "ftrl0": (FTRL, False, False, dict(_BASE, l1=0.01, l2=0.01, fbeta=1.0, ftrl_mode=0)),
     "ftrl1_skip": (FTRL, False, True, dict(_BASE, l1=0.01, l2=0.01, fbeta=1.0, ftrl_mode=1)),
 }
+SPARSE_HP = tuple(HP_SETS)  # the sets the sparse-row cases run (and seed by): fixed, whatever is added below
+# the dense shard tests (dense_oracle.py) add FTRL at l1 = 0.5, where randn z puts a large share of the
+# elements on either side of the |z| <= l1 branch; the other dense sets are the sparse ones
+HP_SETS.update({
+    "ftrl0_dense": (FTRL, False, False, dict(_BASE, l1=0.5, l2=0.01, fbeta=1.0, ftrl_mode=0)),
+    "ftrl1_dense": (FTRL, False, False, dict(_BASE, l1=0.5, l2=0.01, fbeta=1.0, ftrl_mode=1)),
+})
+DENSE_HP = ("sgd", "sgd_momentum", "sgd_nesterov", "adam", "adamw", "adagrad", "ftrl0_dense", "ftrl1_dense")
 HP_SHORT = ("adagrad_rowwise", "adam", "ftrl1_skip")
 OPT_DIMS = (4, 16, 128, 256, 12, 10, 260)
 OPT_DIMS_ALL_HP = (10, 128)
@@ -63,7 +71,7 @@ def opt_cases():
     """(dim, gradient dtype, hyper-parameter set, form) of every small sparse_opt case."""
     out = []
     for dim in OPT_DIMS:
-        for hp in (HP_SETS if dim in OPT_DIMS_ALL_HP else HP_SHORT):
+        for hp in (SPARSE_HP if dim in OPT_DIMS_ALL_HP else HP_SHORT):
             for gdt in GDTYPES:
                 for form in FORMS:
                     out.append((dim, gdt, hp, form))
@@ -163,7 +171,7 @@ def build_opt(dim, gdt, hpname, form, rows_total=300, n=900, seed=0):
     """One sparse_opt case: dict(kind, rowwise, skip_zero, hp, table, st0, st1, rows, grad, perm,
     ncount (int or None), named (bool [rows_total]: rows the live entries name))."""
     kind, rowwise, skip_zero, hp = HP_SETS[hpname]
-    seed = seed + 1000 * dim + 7 * sorted(HP_SETS).index(hpname)
+    seed = seed + 1000 * dim + 7 * sorted(SPARSE_HP).index(hpname)
     table = torch.randn(rows_total, dim, generator=_gen(seed + 1))
     st0, st1 = build_states(kind, rowwise, rows_total, dim, seed + 2, hp.get("momentum", 0.0))
     grad = build_grad(n, dim, GDTYPES[gdt], seed + 3)

@@ -13,6 +13,8 @@ from ps_amd.ops import nn_ops as N
 from ps_amd.ops import reduce as R
 from ps_amd.ops import sparse as S
 
+from . import dense_oracle as do
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -183,7 +185,19 @@ def test_onebit_momentum_pack(n, mdt):
     C.onebit_pack(g.to(DEV), ge, gw, gs, gm, 0.9)
     tol = dict(rtol=1e-2, atol=1e-3) if mdt == torch.bfloat16 else dict(rtol=1e-5, atol=1e-5)
     torch.testing.assert_close(gm.cpu().float(), rm.float(), **tol)
-    assert (gw.cpu() != rw).sum() <= (0 if mdt == torch.float32 else nw // 50)  # bf16 m: rare sign ties differ
+    # signs, per element against the fp64 oracle: equal wherever fp32 rounding of m cannot turn the sign of
+    # c = m + e (|c| > 2^-21 (|m| + |g| + |e|); at most 4 elements lie inside that margin), and on those few
+    # the stored error still belongs to the bit the kernel stored
+    o = do.onebit_pack64(g, err, mom, 0.9)
+    safe = do.pack_margin(o, g, err, mom)
+    bits = do.unpack_bits(gw.cpu(), n)
+    assert int((~safe).sum()) <= 4
+    assert torch.equal(bits[safe], o["bits"][safe]) and torch.equal(gw.cpu(), do.pack_words(bits))
+    o = do.onebit_pack64(g, err, mom, 0.9, bits=bits)
+    _, eb = do.pack_bounds(o, mdt == torch.bfloat16)
+    assert bool(((ge.cpu().double() - o["err"]).abs()[~safe] <= eb[~safe]).all())
+    if mdt == torch.float32:
+        assert torch.equal(gw.cpu(), rw)
     torch.testing.assert_close(gs.cpu(), rs, rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(ge.cpu().float(), re.float(), **tol)
     m2 = mom.to(DEV)
