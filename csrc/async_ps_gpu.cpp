@@ -14,7 +14,6 @@
 #include <torch/extension.h>
 
 #include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <deque>
@@ -56,10 +55,11 @@ class GpuAsyncServer {
   ~GpuAsyncServer() { stop(); }
 
   // [lo, hi) of the shard with its own kernel kind, state tensors (segment-sized) and
-  // hyper-parameters (ps_amd/parallel/plane.py order); bias_mode 0 none, 1 1-beta^t, 2 constant
+  // hyper-parameters (csrc/include/psamd_opt_hyper.h order); bias_mode as opt_bias_correct takes it
   void add_segment(int64_t kind, int64_t lo, int64_t hi, c10::optional<Tensor> st0, c10::optional<Tensor> st1,
                    std::vector<double> h, int64_t bias_mode) {
-    TORCH_CHECK(h.size() == 16, "16 hyper-parameters");
+    TORCH_CHECK(psamd::opt_kind_valid(kind), "optimizer kind must be 0..3, got ", kind);
+    TORCH_CHECK(h.size() == static_cast<size_t>(psamd::kOptHyperLen), psamd::kOptHyperLen, " hyper-parameters");
     TORCH_CHECK(lo >= 0 && hi <= master_.numel() && lo < hi, "segment range");
     Seg sg;
     sg.lo = lo;
@@ -78,10 +78,8 @@ class GpuAsyncServer {
     a.g_bf16 = bf16_;
     a.wout_bf16 = bf16_;
     a.n = hi - lo;
-    a.lr = h[0]; a.beta1 = h[1]; a.beta2 = h[2]; a.eps = h[3]; a.wd = h[4]; a.momentum = h[5];
-    a.dampening = h[6]; a.nesterov = h[7] != 0.0; a.adamw = h[8] != 0.0; a.bc1 = h[9]; a.bc2 = h[10];
-    a.l1 = h[11]; a.l2 = h[12]; a.fbeta = h[13]; a.ftrl_mode = static_cast<int>(h[14]);
-    a.gscale = static_cast<float>(h[15] * gscale_);
+    h.back() *= gscale_;  // gscale, the last field: the server's multiplier goes in before the rounding to float
+    a.h = psamd::opt_hyper_decode(h);
     a.gscale_ptr = nullptr;
     segs_.push_back(sg);
   }
@@ -99,13 +97,7 @@ class GpuAsyncServer {
         char* out = static_cast<char*>(pub_[static_cast<size_t>(slot)].data_ptr());
         for (const Seg& sg : segs_) {
           psamd::FusedOptArgs a = sg.a;
-          if (sg.bias_mode == 1) {
-            a.bc1 = 1.f / (1.f - std::pow(static_cast<double>(a.beta1), static_cast<double>(step)));
-            a.bc2 = 1.f / (1.f - std::pow(static_cast<double>(a.beta2), static_cast<double>(step)));
-          } else if (sg.bias_mode == 2) {
-            a.bc1 = 1.f / (1.f - a.beta1);
-            a.bc2 = 1.f / (1.f - a.beta2);
-          }
+          psamd::opt_bias_correct(a.h, sg.bias_mode, step);
           a.wout = out + sg.lo * esize_;
           // the mailbox was written by a peer GPU's copy kernel: the multi-source form (one
           // source) starts with the system-scope acquire that keeps stale lines out

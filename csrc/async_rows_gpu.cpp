@@ -21,7 +21,6 @@
 
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -89,21 +88,20 @@ class GpuRowService {
     hi_ = static_cast<float>(hi);
   }
 
-  // row updater: kernel kind, the 16 hyper-parameters (ps_amd/parallel/plane.py order), bias
-  // mode (0 none, 1 1 - beta^t per applied push, 2 constant), row-wise accumulator, FTRL skip
+  // row updater: kernel kind, the hyper-parameters (csrc/include/psamd_opt_hyper.h order), bias
+  // mode (opt_bias_correct, per applied push), row-wise accumulator, FTRL skip
   void set_updater(int64_t kind, std::vector<double> h, int64_t bias_mode, bool rowwise, bool skip_zero,
                    double gscale) {
     // The hyper-parameters are a snapshot: the thread copies a_ per push without a lock, so
     // they may only change while it is stopped (AsyncRowTable.set_updater stops and restarts
     // the service around a reconfiguration).
     TORCH_CHECK(!running(), "row service: set_updater while the service thread runs (stop() first)");
-    TORCH_CHECK(h.size() == 16, "16 hyper-parameters");
+    TORCH_CHECK(psamd::opt_kind_valid(kind), "optimizer kind must be 0..3, got ", kind);
+    TORCH_CHECK(h.size() == static_cast<size_t>(psamd::kOptHyperLen), psamd::kOptHyperLen, " hyper-parameters");
     a_ = psamd::SparseOptArgs{};
     a_.kind = static_cast<int>(kind);
-    a_.lr = h[0]; a_.beta1 = h[1]; a_.beta2 = h[2]; a_.eps = h[3]; a_.wd = h[4]; a_.momentum = h[5];
-    a_.dampening = h[6]; a_.nesterov = h[7] != 0.0; a_.adamw = h[8] != 0.0; a_.bc1 = h[9]; a_.bc2 = h[10];
-    a_.l1 = h[11]; a_.l2 = h[12]; a_.fbeta = h[13]; a_.ftrl_mode = static_cast<int>(h[14]);
-    a_.gscale = static_cast<float>(h[15] * gscale);
+    h.back() *= gscale;  // gscale, the last field: the service's multiplier goes in before the rounding to float
+    a_.h = psamd::opt_hyper_decode(h);
     a_.rowwise = rowwise ? 1 : 0;
     a_.skip_zero = skip_zero ? 1 : 0;
     bias_mode_ = static_cast<int>(bias_mode);
@@ -186,13 +184,7 @@ class GpuRowService {
     if (n > 0) {
       slots_of(keys, n, s);
       psamd::SparseOptArgs a = a_;
-      if (bias_mode_ == 1) {
-        a.bc1 = static_cast<float>(1.0 / (1.0 - std::pow(static_cast<double>(a.beta1), static_cast<double>(step))));
-        a.bc2 = static_cast<float>(1.0 / (1.0 - std::pow(static_cast<double>(a.beta2), static_cast<double>(step))));
-      } else if (bias_mode_ == 2) {
-        a.bc1 = 1.f / (1.f - a.beta1);
-        a.bc2 = 1.f / (1.f - a.beta2);
-      }
+      psamd::opt_bias_correct(a.h, bias_mode_, step);
       a.table = table_.data_ptr<float>();
       a.st0 = st0_.defined() ? st0_.data_ptr<float>() : nullptr;
       a.st1 = st1_.defined() ? st1_.data_ptr<float>() : nullptr;

@@ -72,30 +72,38 @@ T* opt_ptr(const c10::optional<Tensor>& t) {
 }
 
 // ------------------------------------------------------------------------------ optimizers
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// The optimizer bindings' one refusal of a kind and of the states it needs; -> the decoded
+// hyper-parameter vector (ps_amd/ops/optim.py hyper_vec, csrc/include/psamd_opt_hyper.h)
+psamd::OptHyper check_opt(int64_t kind, const c10::optional<Tensor>& st0, const c10::optional<Tensor>& st1,
+                          const std::vector<double>& h) {
+  TORCH_CHECK(psamd::opt_kind_valid(kind), "optimizer kind must be 0..3, got ", kind);
+  const psamd::OptHyper hy = psamd::opt_hyper_decode(h);
+  if (kind == 1 || kind == 3) TORCH_CHECK(has(st0) && has(st1), "adam/ftrl need 2 states");
+  if (kind == 2) TORCH_CHECK(has(st0), "adagrad needs a state");
+  if (kind == 0 && hy.momentum != 0.f) TORCH_CHECK(has(st0), "momentum sgd needs a buffer");
+  return hy;
+}
+
 void fused_opt(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::optional<Tensor> st1, Tensor g,
-               c10::optional<Tensor> wout, double lr, double beta1, double beta2, double eps, double wd,
-               double momentum, double dampening, bool nesterov, bool adamw, double bc1, double bc2, double l1,
-               double l2, double fbeta, int64_t ftrl_mode, double gscale, c10::optional<Tensor> gscale_t) {
+               c10::optional<Tensor> wout, std::vector<double> h, c10::optional<Tensor> gscale_t) {
   check_f32(w, "w");
   check_gpu(g, "g");
   const int64_t n = w.numel();
   TORCH_CHECK(g.numel() == n, "grad numel ", g.numel(), " != weight numel ", n);
-  if (st0.has_value() && st0->defined()) { check_f32(*st0, "st0"); TORCH_CHECK(st0->numel() == n, "st0 size"); }
-  if (st1.has_value() && st1->defined()) { check_f32(*st1, "st1"); TORCH_CHECK(st1->numel() == n, "st1 size"); }
-  if ((kind == 1 || kind == 3)) {
-    TORCH_CHECK(st0.has_value() && st0->defined() && st1.has_value() && st1->defined(), "adam/ftrl need 2 states");
-  }
-  if (kind == 2) TORCH_CHECK(st0.has_value() && st0->defined(), "adagrad needs a state");
-  if (kind == 0 && momentum != 0.0) TORCH_CHECK(st0.has_value() && st0->defined(), "momentum sgd needs a buffer");
+  if (has(st0)) { check_f32(*st0, "st0"); TORCH_CHECK(st0->numel() == n, "st0 size"); }
+  if (has(st1)) { check_f32(*st1, "st1"); TORCH_CHECK(st1->numel() == n, "st1 size"); }
   int wout_bf16 = 0;
-  if (wout.has_value() && wout->defined()) {
+  if (has(wout)) {
     check_gpu(*wout, "wout");
     TORCH_CHECK(wout->numel() == n, "wout size");
     wout_bf16 = dcode(*wout, "wout");
   }
-  if (gscale_t.has_value() && gscale_t->defined()) check_f32(*gscale_t, "gscale_t");
-  const c10::DeviceGuard guard(w.device());
+  if (has(gscale_t)) check_f32(*gscale_t, "gscale_t");
   psamd::FusedOptArgs a;
+  a.h = check_opt(kind, st0, st1, h);
+  const c10::DeviceGuard guard(w.device());
   a.kind = static_cast<int>(kind);
   a.w = w.data_ptr<float>();
   a.st0 = opt_ptr<float>(st0);
@@ -105,10 +113,6 @@ void fused_opt(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::optional<
   a.wout = opt_ptr<void>(wout);
   a.wout_bf16 = wout_bf16;
   a.n = n;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.momentum = momentum;
-  a.dampening = dampening; a.nesterov = nesterov; a.adamw = adamw; a.bc1 = bc1; a.bc2 = bc2;
-  a.l1 = l1; a.l2 = l2; a.fbeta = fbeta; a.ftrl_mode = static_cast<int>(ftrl_mode);
-  a.gscale = gscale;
   a.gscale_ptr = opt_ptr<const float>(gscale_t);
   psamd::launch_fused_opt(a, cur_stream(w));
 }
@@ -171,31 +175,26 @@ void check_phase(const Tensor& t, int64_t off, const char* name) {
 }
 
 void fused_opt_multi(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::optional<Tensor> st1,
-                     std::vector<Tensor> srcs, int64_t off, c10::optional<Tensor> wout, double lr, double beta1,
-                     double beta2, double eps, double wd, double momentum, double dampening, bool nesterov,
-                     bool adamw, double bc1, double bc2, double l1, double l2, double fbeta, int64_t ftrl_mode,
-                     double gscale, c10::optional<Tensor> gscale_t, c10::optional<Tensor> words,
-                     c10::optional<Tensor> scales) {
+                     std::vector<Tensor> srcs, int64_t off, c10::optional<Tensor> wout, std::vector<double> h,
+                     c10::optional<Tensor> gscale_t, c10::optional<Tensor> words, c10::optional<Tensor> scales) {
   check_f32(w, "w");
   const int64_t n = w.numel();
-  TORCH_CHECK(kind >= 0 && kind <= 3, "kind must be 0..3");
-  const bool has0 = st0.has_value() && st0->defined(), has1 = st1.has_value() && st1->defined();
+  const bool has0 = has(st0), has1 = has(st1);
   for (const auto* st : {&st0, &st1}) {
-    if (!st->has_value() || !(*st)->defined()) continue;
+    if (!has(*st)) continue;
     check_f32(**st, "st0 / st1");
     TORCH_CHECK((*st)->numel() == n && (*st)->device() == w.device(), "st0 / st1: w's size and device");
   }
-  if (kind == 1 || kind == 3) TORCH_CHECK(has0 && has1, "adam/ftrl need 2 states");
-  if (kind == 2) TORCH_CHECK(has0, "adagrad needs a state");
-  if (kind == 0 && momentum != 0.0) TORCH_CHECK(has0, "momentum sgd needs a buffer");
+  psamd::FusedOptArgs a;
+  a.h = check_opt(kind, st0, st1, h);
   int wout_bf16 = 0;
-  const bool haso = wout.has_value() && wout->defined();
+  const bool haso = has(wout);
   if (haso) {
     check_gpu(*wout, "wout");
     TORCH_CHECK(wout->numel() == n && wout->device() == w.device(), "wout size / device");
     wout_bf16 = dcode(*wout, "wout");
   }
-  if (gscale_t.has_value() && gscale_t->defined()) {
+  if (has(gscale_t)) {
     check_f32(*gscale_t, "gscale_t");
     TORCH_CHECK(gscale_t->numel() >= 1 && gscale_t->device() == w.device(), "gscale_t: float[1] on w's device");
   }
@@ -206,7 +205,6 @@ void fused_opt_multi(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::opt
   if (has1) check_phase(*st1, off, "st1");
   if (haso) check_phase(*wout, off, "wout");
   const c10::DeviceGuard guard(w.device());
-  psamd::FusedOptArgs a;
   a.kind = static_cast<int>(kind);
   a.w = w.data_ptr<float>();
   a.st0 = opt_ptr<float>(st0);
@@ -216,10 +214,6 @@ void fused_opt_multi(int64_t kind, Tensor w, c10::optional<Tensor> st0, c10::opt
   a.wout = opt_ptr<void>(wout);
   a.wout_bf16 = wout_bf16;
   a.n = n;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.momentum = momentum;
-  a.dampening = dampening; a.nesterov = nesterov; a.adamw = adamw; a.bc1 = bc1; a.bc2 = bc2;
-  a.l1 = l1; a.l2 = l2; a.fbeta = fbeta; a.ftrl_mode = static_cast<int>(ftrl_mode);
-  a.gscale = gscale;
   a.gscale_ptr = opt_ptr<const float>(gscale_t);
   psamd::launch_fused_opt_multi(a, m, cur_stream(w));
 }
@@ -236,9 +230,7 @@ void reduce_multi(std::vector<Tensor> srcs, int64_t off, int64_t n, Tensor out, 
 }
 
 void sparse_opt(int64_t kind, Tensor table, c10::optional<Tensor> st0, c10::optional<Tensor> st1, Tensor rows,
-                Tensor grad, bool rowwise, bool skip_zero, double lr, double beta1, double beta2, double eps,
-                double wd, double momentum, double dampening, bool nesterov, bool adamw, double bc1, double bc2,
-                double l1, double l2, double fbeta, int64_t ftrl_mode, double gscale, c10::optional<Tensor> perm,
+                Tensor grad, bool rowwise, bool skip_zero, std::vector<double> h, c10::optional<Tensor> perm,
                 c10::optional<Tensor> ncount) {
   check_f32(table, "table");
   TORCH_CHECK(table.dim() == 2, "table must be [rows, dim]");
@@ -246,20 +238,19 @@ void sparse_opt(int64_t kind, Tensor table, c10::optional<Tensor> st0, c10::opti
   check_gpu(grad, "grad");
   const int64_t dim = table.size(1);
   TORCH_CHECK(grad.numel() == rows.numel() * dim, "grad must be [nrows, dim]");
-  if (perm.has_value() && perm->defined()) {
+  if (has(perm)) {
     check_i64(*perm, "perm");
     TORCH_CHECK(perm->numel() == rows.numel(), "perm must have one entry per row entry");
   }
-  if (st0.has_value() && st0->defined()) {
+  if (has(st0)) {
     check_f32(*st0, "st0");
     const int64_t want = (kind == 2 && rowwise) ? table.size(0) : table.numel();
     TORCH_CHECK(st0->numel() == want, "st0 size (rowwise adagrad state is [rows])");
   }
-  if (st1.has_value() && st1->defined()) { check_f32(*st1, "st1"); TORCH_CHECK(st1->numel() == table.numel(), "st1"); }
-  if (kind == 1 || kind == 3) TORCH_CHECK(st0.has_value() && st1.has_value(), "adam/ftrl need 2 states");
-  if (kind == 2) TORCH_CHECK(st0.has_value(), "adagrad needs a state");
-  const c10::DeviceGuard guard(table.device());
+  if (has(st1)) { check_f32(*st1, "st1"); TORCH_CHECK(st1->numel() == table.numel(), "st1"); }
   psamd::SparseOptArgs a;
+  a.h = check_opt(kind, st0, st1, h);
+  const c10::DeviceGuard guard(table.device());
   a.kind = static_cast<int>(kind);
   a.table = table.data_ptr<float>();
   a.st0 = opt_ptr<float>(st0);
@@ -272,11 +263,7 @@ void sparse_opt(int64_t kind, Tensor table, c10::optional<Tensor> st0, c10::opti
   a.dim = static_cast<int>(dim);
   a.rowwise = rowwise;
   a.skip_zero = skip_zero;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.momentum = momentum;
-  a.dampening = dampening; a.nesterov = nesterov; a.adamw = adamw;
-  a.bc1 = bc1; a.bc2 = bc2; a.l1 = l1; a.l2 = l2; a.fbeta = fbeta; a.ftrl_mode = static_cast<int>(ftrl_mode);
-  a.gscale = gscale;
-  if (ncount.has_value() && ncount->defined()) {  // device count of the live rows (a touched list)
+  if (has(ncount)) {  // device count of the live rows (a touched list)
     check_gpu(*ncount, "ncount");
     TORCH_CHECK(ncount->scalar_type() == torch::kInt32 && ncount->numel() == 1, "ncount: int32 [1]");
     a.ncount = ncount->data_ptr<int32_t>();
@@ -1561,8 +1548,6 @@ std::vector<int64_t> conv_gemm_plan(int64_t M, int64_t N, int64_t C, std::vector
   return {pl.bm, pl.bn, pl.gm};
 }
 
-static bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
-
 // c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> [c, BN partials [slabs, G, N] (epi_writes_sums)]
 // epi: psamd::ConvEpi (module attribute EPI); the prologue follows from pro / a2 / bwd (psamd::ConvPro)
 std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10::optional<Tensor> pro, int64_t epi,
@@ -2042,10 +2027,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_opt_multi", &fused_opt_multi);
   m.def("reduce_multi", &reduce_multi);
   m.def("sparse_opt", &sparse_opt, py::arg("kind"), py::arg("table"), py::arg("st0"), py::arg("st1"),
-        py::arg("rows"), py::arg("grad"), py::arg("rowwise"), py::arg("skip_zero"), py::arg("lr"), py::arg("beta1"),
-        py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("momentum"), py::arg("dampening"),
-        py::arg("nesterov"), py::arg("adamw"), py::arg("bc1"), py::arg("bc2"), py::arg("l1"), py::arg("l2"),
-        py::arg("fbeta"), py::arg("ftrl_mode"), py::arg("gscale"), py::arg("perm") = py::none(), py::arg("ncount") = py::none());
+        py::arg("rows"), py::arg("grad"), py::arg("rowwise"), py::arg("skip_zero"), py::arg("h"),
+        py::arg("perm") = py::none(), py::arg("ncount") = py::none());
+  m.attr("OPT_HYPER_FIELDS") =
+      std::vector<std::string>(psamd::kOptHyperNames, psamd::kOptHyperNames + psamd::kOptHyperLen);
   m.def("sumsq", &sumsq);
   m.def("clip_factor", &clip_factor);
   m.def("cast_", &cast_);

@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "psamd_opt_hyper.h"
+
 namespace psamd {
 
 // ---------------------------------------------------------------- optim.hip
@@ -23,13 +25,8 @@ struct FusedOptArgs {
   void* wout;  // optional weight copy-out (pull buffer), bf16 (wout_bf16) or fp32
   int wout_bf16;
   int64_t n;
-  float lr, beta1, beta2, eps, wd, momentum, dampening;
-  int nesterov, adamw;
-  float bc1, bc2;
-  float l1, l2, fbeta;
-  int ftrl_mode;
-  float gscale;
-  const float* gscale_ptr;
+  OptHyper h;
+  const float* gscale_ptr;  // optional device multiplier of the gradient (global-norm clip factor)
 };
 void launch_fused_opt(const FusedOptArgs& a, hipStream_t s);
 
@@ -103,12 +100,8 @@ struct SparseOptArgs {
   int64_t nrows;
   int dim;
   int rowwise;  // adagrad: one accumulator per row
-  int skip_zero;
-  float lr, beta1, beta2, eps, wd, momentum, dampening;
-  int nesterov, adamw;
-  float bc1, bc2, l1, l2, fbeta;
-  int ftrl_mode;
-  float gscale;
+  int skip_zero;  // FTRL: skip a row whose first gradient element is 0 (reference)
+  OptHyper h;
   const int32_t* ncount = nullptr;  // nullable device count: only rows [0, min(nrows, *ncount)) are live
 };
 void launch_sparse_opt(const SparseOptArgs& a, hipStream_t s);

@@ -16,6 +16,7 @@
 //                                                        canonical McMahan FTRL-proximal -> ftrl_mode = 0
 //   Adagrad      (north-star, DLRM tables)
 #include <cstdlib>
+#include <type_traits>
 
 #include "psamd_device.h"
 #include "psamd_launch.h"
@@ -28,20 +29,24 @@ static int opt_grid(int64_t work_items, int block) { return stream_grid(work_ite
 
 enum OptKind : int { kSGD = 0, kAdam = 1, kAdagrad = 2, kFtrl = 3 };
 
-struct OptParams {
-  float lr;
-  float beta1, beta2, eps;
-  float wd;
-  float momentum, dampening;
-  int nesterov;
-  int adamw;
-  float bc1, bc2;      // multipliers applied to m and v (bias correction), host-computed
-  float l1, l2, fbeta; // FTRL
-  int ftrl_mode;       // 0 canonical, 1 reference
-  int skip_zero;       // FTRL: skip the update when the first grad element of the key is 0 (reference)
-  float gscale;        // host gradient multiplier
+// The kernels' by-value argument: the launch's OptHyper, then {skip_zero, gscale_ptr} of its args.
+struct OptParams : OptHyper {
+  int skip_zero;            // FTRL: skip the update when the first grad element of the key is 0 (reference)
   const float* gscale_ptr;  // optional device multiplier (global-norm clip factor)
 };
+
+// f(std::integral_constant<int, KIND>) for the launch's kind; the callers (csrc/bindings.cpp, the
+// engines' set-up calls) refuse a kind that !opt_kind_valid before it gets here
+template <typename F>
+static void with_kind(int kind, F f) {
+  switch (kind) {
+    case kSGD: f(std::integral_constant<int, kSGD>{}); break;
+    case kAdam: f(std::integral_constant<int, kAdam>{}); break;
+    case kAdagrad: f(std::integral_constant<int, kAdagrad>{}); break;
+    case kFtrl: f(std::integral_constant<int, kFtrl>{}); break;
+    default: break;
+  }
+}
 
 template <int KIND>
 __device__ __forceinline__ void opt_apply(float& w, float g, float& s0, float& s1, const OptParams& p) {
@@ -185,25 +190,10 @@ static void dispatch_grad(const FusedOptArgs& a, const OptParams& p, hipStream_t
   else dispatch_out<KIND, float>(a, p, s);
 }
 
-static OptParams opt_params(const FusedOptArgs& a) {
-  OptParams p;
-  p.lr = a.lr; p.beta1 = a.beta1; p.beta2 = a.beta2; p.eps = a.eps; p.wd = a.wd;
-  p.momentum = a.momentum; p.dampening = a.dampening; p.nesterov = a.nesterov; p.adamw = a.adamw;
-  p.bc1 = a.bc1; p.bc2 = a.bc2; p.l1 = a.l1; p.l2 = a.l2; p.fbeta = a.fbeta; p.ftrl_mode = a.ftrl_mode;
-  p.skip_zero = 0; p.gscale = a.gscale; p.gscale_ptr = a.gscale_ptr;
-  return p;
-}
-
 void launch_fused_opt(const FusedOptArgs& a, hipStream_t s) {
   if (a.n <= 0) return;
-  const OptParams p = opt_params(a);
-  switch (a.kind) {
-    case kSGD: dispatch_grad<kSGD>(a, p, s); break;
-    case kAdam: dispatch_grad<kAdam>(a, p, s); break;
-    case kAdagrad: dispatch_grad<kAdagrad>(a, p, s); break;
-    case kFtrl: dispatch_grad<kFtrl>(a, p, s); break;
-    default: break;
-  }
+  const OptParams p{a.h, 0, a.gscale_ptr};
+  with_kind(a.kind, [&](auto k) { dispatch_grad<decltype(k)::value>(a, p, s); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -341,18 +331,12 @@ static void launch_multi_kind(const FusedOptArgs& a, const MultiGrad& m, const O
 
 void launch_fused_opt_multi(const FusedOptArgs& a, const MultiGrad& m, hipStream_t s) {
   if (a.n <= 0) return;
-  const OptParams p = opt_params(a);
+  const OptParams p{a.h, 0, a.gscale_ptr};
   // elements before the first 8-aligned chunk index are done element-wise (every array of the
   // segment shares the phase of m.off: masters / states / wout start at the segment too)
   int64_t head = (8 - (m.off & 7)) & 7;
   if (head > a.n) head = a.n;
-  switch (a.kind) {
-    case kSGD: launch_multi_kind<kSGD>(a, m, p, head, s); break;
-    case kAdam: launch_multi_kind<kAdam>(a, m, p, head, s); break;
-    case kAdagrad: launch_multi_kind<kAdagrad>(a, m, p, head, s); break;
-    case kFtrl: launch_multi_kind<kFtrl>(a, m, p, head, s); break;
-    default: break;
-  }
+  with_kind(a.kind, [&](auto k) { launch_multi_kind<decltype(k)::value>(a, m, p, head, s); });
 }
 
 // Reduce-only form (global-norm clipping needs the whole reduced gradient before any update):
@@ -547,55 +531,32 @@ static int vec_lanes_log2(int dim) {  // lanes per row for the vectorised kernel
   return lg;
 }
 
+// lg >= 0: the vectorised kernel with 2^lg lanes per row; -1: the scalar kernel
+template <int KIND, typename G>
+static void launch_sparse_kind(const SparseOptArgs& a, const OptParams& p, int lg, hipStream_t s) {
+  const G* grad = static_cast<const G*>(a.grad);
+  const int block = 256;
+  if (lg >= 0) {
+    const int grid = stream_grid(((a.nrows << lg) + 63) / 64 * 64, block);
+    hipLaunchKernelGGL((sparse_opt_vec_kernel<KIND, G>), dim3(grid), dim3(block), 0, s, a.table, a.st0, a.st1, a.rows,
+                       a.perm, grad, a.nrows, a.dim, lg, p, a.rowwise, a.ncount);
+  } else {
+    const int grid = stream_grid(a.nrows * 64, block);
+    hipLaunchKernelGGL((sparse_opt_kernel<KIND, G>), dim3(grid), dim3(block), 0, s, a.table, a.st0, a.st1, a.rows,
+                       a.perm, grad, a.nrows, a.dim, p, a.rowwise, a.ncount);
+  }
+}
+
 void launch_sparse_opt(const SparseOptArgs& a, hipStream_t s) {
   if (a.nrows <= 0) return;
-  OptParams p;
-  p.lr = a.lr; p.beta1 = a.beta1; p.beta2 = a.beta2; p.eps = a.eps; p.wd = a.wd;
-  p.momentum = a.momentum; p.dampening = a.dampening; p.nesterov = a.nesterov; p.adamw = a.adamw;
-  p.bc1 = a.bc1; p.bc2 = a.bc2; p.l1 = a.l1; p.l2 = a.l2; p.fbeta = a.fbeta; p.ftrl_mode = a.ftrl_mode;
-  p.skip_zero = a.skip_zero; p.gscale = a.gscale; p.gscale_ptr = nullptr;
-  const int block = 256;
-  const int lg = vec_lanes_log2(a.dim);
+  const OptParams p{a.h, a.skip_zero, nullptr};
   const bool aligned = ((reinterpret_cast<uintptr_t>(a.table) | reinterpret_cast<uintptr_t>(a.st0) |
                          reinterpret_cast<uintptr_t>(a.st1) | reinterpret_cast<uintptr_t>(a.grad)) & 15) == 0;
-  if (lg >= 0 && aligned) {
-    const int grid = stream_grid(((a.nrows << lg) + 63) / 64 * 64, block);
-#define PSAMD_SPARSE_VEC(K)                                                                                      \
-  if (a.g_bf16)                                                                                                  \
-    hipLaunchKernelGGL((sparse_opt_vec_kernel<K, uint16_t>), dim3(grid), dim3(block), 0, s, a.table, a.st0,      \
-                       a.st1, a.rows, a.perm, static_cast<const uint16_t*>(a.grad), a.nrows, a.dim, lg, p,     \
-                       a.rowwise, a.ncount);                                                                     \
-  else                                                                                                           \
-    hipLaunchKernelGGL((sparse_opt_vec_kernel<K, float>), dim3(grid), dim3(block), 0, s, a.table, a.st0, a.st1, \
-                       a.rows, a.perm, static_cast<const float*>(a.grad), a.nrows, a.dim, lg, p, a.rowwise,    \
-                       a.ncount);
-    switch (a.kind) {
-      case kSGD: PSAMD_SPARSE_VEC(kSGD); break;
-      case kAdam: PSAMD_SPARSE_VEC(kAdam); break;
-      case kAdagrad: PSAMD_SPARSE_VEC(kAdagrad); break;
-      case kFtrl: PSAMD_SPARSE_VEC(kFtrl); break;
-      default: break;
-    }
-#undef PSAMD_SPARSE_VEC
-    return;
-  }
-  const int grid = stream_grid(a.nrows * 64, block);
-#define PSAMD_SPARSE_LAUNCH(K)                                                                                  \
-  if (a.g_bf16)                                                                                                 \
-    hipLaunchKernelGGL((sparse_opt_kernel<K, uint16_t>), dim3(grid), dim3(block), 0, s, a.table, a.st0, a.st1,  \
-                       a.rows, a.perm, static_cast<const uint16_t*>(a.grad), a.nrows, a.dim, p, a.rowwise,      \
-                       a.ncount);                                                                               \
-  else                                                                                                          \
-    hipLaunchKernelGGL((sparse_opt_kernel<K, float>), dim3(grid), dim3(block), 0, s, a.table, a.st0, a.st1,     \
-                       a.rows, a.perm, static_cast<const float*>(a.grad), a.nrows, a.dim, p, a.rowwise, a.ncount);
-  switch (a.kind) {
-    case kSGD: PSAMD_SPARSE_LAUNCH(kSGD); break;
-    case kAdam: PSAMD_SPARSE_LAUNCH(kAdam); break;
-    case kAdagrad: PSAMD_SPARSE_LAUNCH(kAdagrad); break;
-    case kFtrl: PSAMD_SPARSE_LAUNCH(kFtrl); break;
-    default: break;
-  }
-#undef PSAMD_SPARSE_LAUNCH
+  const int lg = aligned ? vec_lanes_log2(a.dim) : -1;
+  with_kind(a.kind, [&](auto k) {
+    if (a.g_bf16) launch_sparse_kind<decltype(k)::value, uint16_t>(a, p, lg, s);
+    else launch_sparse_kind<decltype(k)::value, float>(a, p, lg, s);
+  });
 }
 
 }  // namespace psamd

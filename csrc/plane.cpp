@@ -51,7 +51,6 @@ using Clock = std::chrono::steady_clock;
 
 constexpr int64_t kPlaneMagic = 0x504c414e45303031ll;  // "PLANE001"
 constexpr int kHdr = 8;
-constexpr int kHyper = 16;  // lr beta1 beta2 eps wd momentum dampening nesterov adamw bc1 bc2 l1 l2 fbeta ftrl gscale
 
 void hip_ok(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
 
@@ -145,6 +144,7 @@ class PlaneEngine {
 
   void add_segment(int64_t b, int64_t uid, int64_t kind, int64_t a, int64_t z, int64_t master, int64_t st0,
                    int64_t st1) {
+    TORCH_CHECK(psamd::opt_kind_valid(kind), "optimizer kind must be 0..3, got ", kind);
     auto& d = buckets_.at(static_cast<size_t>(b));
     d.segs.push_back(Segment{static_cast<int>(uid), static_cast<int>(kind), a, z, reinterpret_cast<float*>(master),
                              reinterpret_cast<float*>(st0), reinterpret_cast<float*>(st1)});
@@ -160,7 +160,7 @@ class PlaneEngine {
   }
 
   void set_hyper(int64_t round, int64_t uid, std::vector<double> h) {
-    TORCH_CHECK(static_cast<int>(h.size()) == kHyper, "hyper vector of ", kHyper);
+    TORCH_CHECK(static_cast<int>(h.size()) == psamd::kOptHyperLen, "hyper vector of ", psamd::kOptHyperLen);
     std::lock_guard<std::mutex> g(mu_);
     auto& v = hyper_[round];
     if (static_cast<int64_t>(v.size()) <= uid) v.resize(static_cast<size_t>(uid + 1));
@@ -762,7 +762,6 @@ class PlaneEngine {
     const float avg = average_ ? 1.f / static_cast<float>(W_) : 1.f;
     const uintptr_t own = bases_[static_cast<size_t>(me_)];
     for (const auto& sg : bk.segs) {
-      const std::vector<double> h = hyper_of(j.round, sg.uid);
       psamd::FusedOptArgs a{};
       a.kind = sg.kind;
       a.w = sg.master;
@@ -772,10 +771,8 @@ class PlaneEngine {
       a.wout = reinterpret_cast<void*>(own + bk.woff[static_cast<size_t>(j.wslot)] + (me_ * bk.chunk + sg.a) * bk.esize);
       a.wout_bf16 = bk.g_bf16;
       a.n = sg.z - sg.a;
-      a.lr = h[0]; a.beta1 = h[1]; a.beta2 = h[2]; a.eps = h[3]; a.wd = h[4]; a.momentum = h[5];
-      a.dampening = h[6]; a.nesterov = h[7] != 0.0; a.adamw = h[8] != 0.0; a.bc1 = h[9]; a.bc2 = h[10];
-      a.l1 = h[11]; a.l2 = h[12]; a.fbeta = h[13]; a.ftrl_mode = static_cast<int>(h[14]);
-      a.gscale = static_cast<float>(h[15]) * avg;
+      a.h = psamd::opt_hyper_decode(hyper_of(j.round, sg.uid));
+      a.h.gscale *= avg;
       if (clipped) {
         a.g = bk.gshard + sg.a;
         a.g_bf16 = 0;
@@ -1097,7 +1094,7 @@ class IpcEvent {
 void register_plane(pybind11::module& m) {
   auto pm = m.def_submodule("plane", "xGMI parameter-server plane (csrc/plane.cpp)");
   pm.attr("MAX_WORLD") = psamd::kPlaneMaxSrc;
-  pm.attr("HYPER") = kHyper;
+  pm.attr("HYPER") = psamd::kOptHyperLen;
   pm.def("ctl_size", [](int64_t W, int64_t NB) { return ctl_words(W, NB) * 8; });
   pm.def("ctl_init", [](uintptr_t addr, int64_t W, int64_t NB) {
     int64_t* b = reinterpret_cast<int64_t*>(addr);

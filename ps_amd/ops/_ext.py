@@ -31,6 +31,15 @@ def _load():
             _build.build()
             _ERR = None
             _C = importlib.import_module("ps_amd._C")
+    if _C is not None:
+        from .optim import HYPER_FIELDS  # here, not at the top: optim imports this module
+
+        built = tuple(getattr(_C, "OPT_HYPER_FIELDS", ()))
+        if built != HYPER_FIELDS:
+            _C = None
+            _ERR = RuntimeError(f"ps_amd._C unpacks the optimizer hyper-parameters as {built}, ops/optim.py packs "
+                                f"{HYPER_FIELDS}: rebuild the extension")
+            raise _ERR
     return _C
 
 

@@ -14,14 +14,25 @@ from ._ext import native, use_native
 SGD, ADAM, ADAGRAD, FTRL = 0, 1, 2, 3
 
 
+# The hyper-parameter record of every optimizer kernel, in the order the extension unpacks it
+# (csrc/include/psamd_opt_hyper.h; ops/_ext.py compares the two when it loads the extension).
+HYPER_DEFAULTS = dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False,
+                      adamw=False, bc1=1.0, bc2=1.0, l1=0.0, l2=0.0, fbeta=1.0, ftrl_mode=0, gscale=1.0)
+HYPER_FIELDS = tuple(HYPER_DEFAULTS)
+
+
 def _hp(kw):
-    d = dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, momentum=0.0, dampening=0.0, nesterov=False,
-             adamw=False, bc1=1.0, bc2=1.0, l1=0.0, l2=0.0, fbeta=1.0, ftrl_mode=0, gscale=1.0)
-    unknown = set(kw) - set(d)
+    unknown = set(kw) - set(HYPER_DEFAULTS)
     if unknown:
         raise TypeError(f"unknown optimizer hyper-parameters {sorted(unknown)}")
-    d.update(kw)
-    return d
+    return {**HYPER_DEFAULTS, **kw}
+
+
+def hyper_vec(hp) -> list:
+    """``hp`` (any subset of HYPER_FIELDS; the rest take their defaults) as the flat list of floats
+    the extension takes, flags as 0.0 / 1.0."""
+    h = _hp(hp)
+    return [float(h[k]) for k in HYPER_FIELDS]
 
 
 def _apply_ref(kind, w, s0, s1, g, h):
@@ -78,12 +89,10 @@ def fused_opt(kind: int, w: torch.Tensor, st0: Optional[torch.Tensor], st1: Opti
     ``wout`` (optional) receives the updated weights (bf16 or fp32) -- the pull buffer.
     ``gscale_t`` (optional, device float[1]) multiplies the gradient (clip factor).
     """
-    h = _hp(hp)
     if use_native(w, g):
-        native().fused_opt(kind, w, st0, st1, g, wout, h["lr"], h["beta1"], h["beta2"], h["eps"], h["wd"],
-                           h["momentum"], h["dampening"], bool(h["nesterov"]), bool(h["adamw"]), h["bc1"],
-                           h["bc2"], h["l1"], h["l2"], h["fbeta"], int(h["ftrl_mode"]), h["gscale"], gscale_t)
+        native().fused_opt(kind, w, st0, st1, g, wout, hyper_vec(hp), gscale_t)
         return
+    h = _hp(hp)
     gg = g.float().reshape(w.shape) * h["gscale"]
     if gscale_t is not None:
         gg = gg * gscale_t.float()
@@ -108,13 +117,11 @@ def sparse_opt(kind: int, table: torch.Tensor, st0: Optional[torch.Tensor], st1:
     gradient rows of every run are summed and ONE update is applied per distinct row (the
     owner-side merge of several workers' / micro-batches' pushes, no host sync).  Negative
     rows are skipped."""
-    h = _hp(hp)
     if use_native(table, grad):
-        native().sparse_opt(kind, table, st0, st1, rows, grad, bool(rowwise), bool(skip_zero), h["lr"], h["beta1"],
-                            h["beta2"], h["eps"], h["wd"], h["momentum"], h["dampening"], bool(h["nesterov"]),
-                            bool(h["adamw"]), h["bc1"], h["bc2"], h["l1"], h["l2"], h["fbeta"], int(h["ftrl_mode"]),
-                            h["gscale"], perm, ncount)
+        native().sparse_opt(kind, table, st0, st1, rows, grad, bool(rowwise), bool(skip_zero), hyper_vec(hp), perm,
+                            ncount)
         return
+    h = _hp(hp)
     if ncount is not None:
         rows = rows[:int(ncount.item())]
         perm = perm[:rows.numel()] if perm is not None else None

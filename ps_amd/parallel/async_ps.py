@@ -284,10 +284,9 @@ class AsyncPS:
             self.server = _C.GpuAsyncServer(self.ctl, me, self.master, [self.mbox[i] for i in range(W * self.MB)],
                                             [self.pub[s] for s in range(3)], self.gscale)
             for (u, a, z), st in zip(self.segs, self.states):
-                h = _o._hp(u.hyper(1))
                 bias = _BIAS_MODE[u.bias_correction] if isinstance(u, AdamUpdater) else 0
                 st2 = list(st) + [None] * (2 - len(st))
-                self.server.add_segment(u.kind, a, z, st2[0], st2[1], [float(h[k]) for k in _HYPER], bias)
+                self.server.add_segment(u.kind, a, z, st2[0], st2[1], _o.hyper_vec(u.hyper(1)), bias)
             self.notifier = _C.GpuNotifier(self.ctl)
             self.push_stream = side_stream(self.device)
             self.pull_stream = torch.cuda.Stream(device=self.device)
@@ -679,7 +678,3 @@ class AsyncPS:
         self._ctl.close()
         if self.rank == 0:
             self._ctl.unlink()
-
-
-_HYPER = ("lr", "beta1", "beta2", "eps", "wd", "momentum", "dampening", "nesterov", "adamw", "bc1", "bc2", "l1", "l2",
-          "fbeta", "ftrl_mode", "gscale")

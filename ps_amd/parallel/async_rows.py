@@ -266,12 +266,11 @@ class AsyncRowTable(TcpSparseTable):
         u = self.updater
         if u is not None:
             from ..ops import optim as _o
-            from .async_ps import _BIAS_MODE, _HYPER
+            from .async_ps import _BIAS_MODE
             from .updaters import AdamUpdater
 
-            h = _o._hp(u.hyper(1))
             bias = _BIAS_MODE[u.bias_correction] if isinstance(u, AdamUpdater) else 0
-            self.service.set_updater(u.kind, [float(h[k]) for k in _HYPER], bias, bool(getattr(u, "rowwise", False)),
+            self.service.set_updater(u.kind, _o.hyper_vec(u.hyper(1)), bias, bool(getattr(u, "rowwise", False)),
                                      getattr(u, "mode", "") == "reference", 1.0 / self.W)
 
     # ------------------------------------------------------------------ config

@@ -295,10 +295,7 @@ class XgmiPlane:
             return
         self._hyper_round = rnd
         for uid, u in enumerate(self._ups):
-            h = _o._hp(u.hyper(rnd + 1))
-            self.engine.set_hyper(rnd, uid, [float(h[k]) for k in (
-                "lr", "beta1", "beta2", "eps", "wd", "momentum", "dampening", "nesterov", "adamw", "bc1", "bc2", "l1",
-                "l2", "fbeta", "ftrl_mode", "gscale")])
+            self.engine.set_hyper(rnd, uid, _o.hyper_vec(u.hyper(rnd + 1)))
 
     def push(self, b: int, rnd: int, gslot: int, wslot: int, onebit: bool) -> None:
         self.begin_round(rnd)

@@ -24,6 +24,7 @@ the launchers can select.
                                          off 5, n = 3 + 8 * 130 + 5, nsrc 2
     test_fused_opt_multi_grid_wrap       off 5, 4 196 717 elements, 2 bf16 srcs   fused_opt_multi_kernel<kSGD, 0, uint16_t, 0>, second turn of the loop
     test_multi_bindings_refuse           host-side checks only                    (nothing is launched)
+    test_opt_bindings_refuse_kind_and_hyper  kind 4 / -1, a 15-element hyper vector   fused_opt, fused_opt_multi, sparse_opt (nothing is launched)
     test_onebit_pack                     n 5 / 64 / 1000 / 1024 / 1029 / 2048 /   onebit_pack_kernel<float | uint16_t, float | uint16_t, MOM false | true>
                                          3001 x g dtype x err dtype x momentum    (full-vector and ragged paths, a block's second chunk absent / present)
     test_onebit_momentum                 g dtype x momentum dtype, n 3001         onebit_momentum_kernel<G, E>
@@ -80,12 +81,6 @@ def _at(x, nbytes=0):
 
 def _cpu(x):
     return None if x is None else x.cpu()
-
-
-def _hp_args(hp):
-    h = do._hp(hp)
-    return (h["lr"], h["beta1"], h["beta2"], h["eps"], h["wd"], h["momentum"], h["dampening"], bool(h["nesterov"]),
-            bool(h["adamw"]), h["bc1"], h["bc2"], h["l1"], h["l2"], h["fbeta"], int(h["ftrl_mode"]), h["gscale"])
 
 
 # ------------------------------------------------------------------------------------ fused_opt
@@ -183,7 +178,7 @@ def _run_multi(c):
     bufs = [None if x is None else x.to(DEV) for x in (c["master"], c["st0"], c["st1"], c["pull"])]
     srcs, words, scales = _sources(c)
     native().fused_opt_multi(c["kind"], seg(bufs[0]), seg(bufs[1]), seg(bufs[2]), srcs, o, seg(bufs[3]),
-                             *_hp_args(c["hp"]), None, words, scales)
+                             ops.hyper_vec(c["hp"]), None, words, scales)
     got = [_cpu(x) for x in bufs]
     do.check_opt(tuple(seg(x) for x in got[:3]), do.multi_opt64(c), c["keep"], do.OPT_TOL)
     if got[3] is not None:
@@ -216,14 +211,14 @@ def test_fused_opt_multi_grid_wrap():
 def test_multi_bindings_refuse():
     """Each refusal is a host-side TORCH_CHECK: a Python exception, and nothing is launched."""
     m = native()
-    hp = _hp_args(do.HP_SETS["sgd"][3])
+    hp = ops.hyper_vec(do.HP_SETS["sgd"][3])
     chunk = torch.ones(1024, device=DEV)
     srcs = [torch.ones(1024, device=DEV) for _ in range(17)]
     words = torch.zeros(1, 32, dtype=torch.int64, device=DEV)
     scales = torch.ones(1, 1, device=DEV)
 
     def opt(w, s, off, wout=None, words=None, scales=None):
-        m.fused_opt_multi(do.SGD, w, None, None, s, off, wout, *hp, None, words, scales)
+        m.fused_opt_multi(do.SGD, w, None, None, s, off, wout, hp, None, words, scales)
 
     good = torch.ones(1024, device=DEV)
     opt(good[8:24], srcs[:1], 8)  # the well-formed call passes and steps
@@ -250,6 +245,33 @@ def test_multi_bindings_refuse():
             call()
     torch.cuda.synchronize()
     assert bool((chunk == 1.0).all())  # nothing ran
+
+
+def test_opt_bindings_refuse_kind_and_hyper():
+    """An optimizer kind outside 0..3 and a hyper-parameter vector of the wrong length are refused on the
+    host by all three bindings; the extension unpacks the vector in the order ops.hyper_vec packs it."""
+    m = native()
+    assert tuple(m.OPT_HYPER_FIELDS) == ops.HYPER_FIELDS
+    hp = ops.hyper_vec(do.HP_SETS["sgd"][3])
+    w, a, b, g = (torch.full((16,), v, device=DEV) for v in (1.0, 2.0, 3.0, 4.0))
+    table, ta, tb, tg = (x.reshape(4, 4) for x in (w, a, b, g))
+    rows = torch.arange(4, device=DEV)
+
+    def calls(kind, h):
+        return [lambda: m.fused_opt(kind, w, a, b, g, None, h, None),
+                lambda: m.fused_opt_multi(kind, w, a, b, [g], 0, None, h, None, None, None),
+                lambda: m.sparse_opt(kind, table, ta, tb, rows, tg, False, False, h)]
+
+    for kind in (4, -1):
+        for call in calls(kind, hp):
+            with pytest.raises(RuntimeError):
+                call()
+    for call in calls(do.SGD, hp[:15]):
+        with pytest.raises(ValueError):
+            call()
+    torch.cuda.synchronize()
+    for x, v in ((w, 1.0), (a, 2.0), (b, 3.0), (g, 4.0)):
+        assert bool((x == v).all())  # nothing ran
 
 
 # --------------------------------------------------------------------------------------- 1-bit
