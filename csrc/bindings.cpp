@@ -1548,6 +1548,26 @@ std::vector<int64_t> conv_gemm_plan(int64_t M, int64_t N, int64_t C, std::vector
   return {pl.bm, pl.bn, pl.gm};
 }
 
+// The kernel family conv_gemm launches (psamd::ConvFwdFamily: 0 big, 1 two-source LDS-DMA, 2 patch, 3 tall,
+// 4 two-source register-staged, 5 LDS-DMA, 6 register-staged); mode: psamd::ConvPro -- no launch
+int64_t conv_gemm_family(int64_t M, int64_t N, int64_t C, std::vector<int64_t> geo, int64_t mode, int64_t epi) {
+  TORCH_CHECK(geo.size() == 7, "geo = [H, W, OH, OW, ks, stride, pad]");
+  TORCH_CHECK(mode >= psamd::kProNone && mode <= psamd::kProBlockOut, "mode: ConvPro 0..3");
+  const psamd::ConvGeo g{static_cast<int>(geo[0]), static_cast<int>(geo[1]), static_cast<int>(geo[2]),
+                         static_cast<int>(geo[3]), static_cast<int>(C), static_cast<int>(geo[4]),
+                         static_cast<int>(geo[5]), static_cast<int>(geo[6])};
+  const int K = static_cast<int>(geo[4] * geo[4] * C), pro = static_cast<int>(mode), e = static_cast<int>(epi);
+  const auto pl = psamd::conv_fwd_plan_geo(static_cast<int>(M), static_cast<int>(N), K, pro != psamd::kProNone, g,
+                                           psamd::pro_src2(pro), e);
+  return psamd::conv_fwd_family(pl, static_cast<int>(M), static_cast<int>(N), K, g, pro, e);
+}
+
+// The grid of conv_dgrad_s2 for dz [M, C2] -> dx [4 M, C1]: [bn, gm] -- the channel tile of
+// conv_dgrad_phases_kernel and the 128-pixel tiles (= partial-sum rows) of each of the four phases
+std::vector<int64_t> conv_dgrad_s2_plan(int64_t M, int64_t C1) {
+  return {C1 % 128 == 0 ? 128 : 64, psamd::conv_dgrad_phase_gm(static_cast<int>(M))};
+}
+
 // c [M, N] = epilogue(sum_k f(a[src(m, k)]) b[n, k]) -> [c, BN partials [slabs, G, N] (epi_writes_sums)]
 // epi: psamd::ConvEpi (module attribute EPI); the prologue follows from pro / a2 / bwd (psamd::ConvPro)
 std::vector<Tensor> conv_gemm(Tensor a, Tensor b, std::vector<int64_t> geo, c10::optional<Tensor> pro, int64_t epi,
@@ -1696,6 +1716,19 @@ bool conv_wgrad_patch_ok(std::vector<int64_t> geo, int64_t images, int64_t N, in
                          static_cast<int>(geo[3]), static_cast<int>(C), static_cast<int>(geo[4]),
                          static_cast<int>(geo[5]), static_cast<int>(geo[6])};
   return psamd::conv_wgrad_patch_ok(g, static_cast<int>(images * geo[2] * geo[3]), static_cast<int>(N), false);
+}
+
+// The plan conv_wgrad picks: [kind, tn, tk, tiles, nsplit, rows_or_stages, groups] (psamd::ConvWgradPlan:
+// kind 0 the 64 / 128 tiles, 1-4 the wide tiles, 5 the 3x3 patch kernel) -- no launch; tests use it to
+// see which kernel and how many slab-reduce levels a shape runs
+std::vector<int64_t> conv_wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t C, std::vector<int64_t> geo, bool pro) {
+  TORCH_CHECK(geo.size() == 7, "geo = [H, W, OH, OW, ks, stride, pad]");
+  TORCH_CHECK(K == geo[4] * geo[4] * C, "K must be ks * ks * C");
+  const psamd::ConvGeo g{static_cast<int>(geo[0]), static_cast<int>(geo[1]), static_cast<int>(geo[2]),
+                         static_cast<int>(geo[3]), static_cast<int>(C), static_cast<int>(geo[4]),
+                         static_cast<int>(geo[5]), static_cast<int>(geo[6])};
+  const auto w = psamd::conv_wgrad_plan(static_cast<int>(M), static_cast<int>(N), static_cast<int>(K), g, pro);
+  return {w.kind, w.tn, w.tk, w.tiles, w.nsplit, w.rows, w.groups};
 }
 
 // Data gradient of a 3x3 / stride-2 / pad-1 convolution as four stride-1 phase GEMMs over dz:
@@ -1998,6 +2031,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("epi") = 0, py::arg("z") = py::none(), py::arg("mc") = py::none(), py::arg("mean") = py::none(),
         py::arg("invstd") = py::none());
   m.def("conv_wgrad", &conv_wgrad, py::arg("dz"), py::arg("x"), py::arg("geo"), py::arg("pro") = py::none());
+  m.def("conv_gemm_family", &conv_gemm_family, py::arg("M"), py::arg("N"), py::arg("C"), py::arg("geo"),
+        py::arg("mode") = 0, py::arg("epi") = 0);
+  m.def("conv_dgrad_s2_plan", &conv_dgrad_s2_plan, py::arg("M"), py::arg("C1"));
+  m.def("conv_wgrad_plan", &conv_wgrad_plan, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("C"), py::arg("geo"),
+        py::arg("pro") = false);
   m.def("conv_wgrad_patch_ok", &conv_wgrad_patch_ok, py::arg("geo"), py::arg("images"), py::arg("N"), py::arg("C"));
   {  // psamd::ConvEpi for ps_amd/ops/convgemm.py Epi
     py::dict epi;

@@ -490,6 +490,17 @@ ConvFwdPlan conv_fwd_plan_geo(int M, int N, int K, bool pro, const ConvGeo& g, i
 // std::invalid_argument where it does not, and the binding checks before it launches
 bool conv_fwd_runs(const ConvFwdPlan& pl, int pro, int epi);
 void launch_conv_fwd(const ConvGemmArgs& a, hipStream_t s);
+// the kernel family launch_conv_fwd runs for plan pl (its ladder branches on this value only)
+enum ConvFwdFamily : int {
+  kFamBig = 0,         // conv_big.hip, 256 x 256 tiles
+  kFamTwosrcGlds = 1,  // two-source prologue, LDS-DMA staging
+  kFamPatch = 2,       // 3x3 patch-staged tiles
+  kFamTall = 3,        // 256 x 64 tiles, LDS-DMA staging
+  kFamTwosrcReg = 4,   // two-source prologue, register staging
+  kFamGlds = 5,        // no prologue, LDS-DMA staging, one tile per block
+  kFamReg = 6          // register staging (persistent grid where the plan says so)
+};
+int conv_fwd_family(const ConvFwdPlan& pl, int M, int N, int K, const ConvGeo& g, int pro, int epi);
 // two-source prologues with K >= 64 x this run on the LDS-DMA variant (convgemm.hip;
 // profiles/r4_twosrc_probe.txt: LDS-DMA ahead at every K >= 256)
 constexpr int kTwosrcGldsMinNk = 4;
@@ -541,6 +552,14 @@ struct ConvWgradArgs {
   FastDiv fd_ohw, fd_ow;  // set by launch_conv_wgrad (OH * OW, OW)
 };
 int conv_wgrad_splits(int M, int N, int K, int C, bool pro);
+// The plan launch_conv_wgrad picks (no db): kind 0 conv_wgrad_kernel, 1-4 the wide tiles (256 x 256,
+// 256 x 128, 128 x 256, 128 x 384), 5 the 3x3 patch kernel; the dW tile tn x tk (output channels x
+// reduction columns), tiles, pixel splits (= fp32 slabs), pixels per split (patch: 112-pixel stages per
+// split) and the first-level slab-reduce groups (0: one reduce level)
+struct ConvWgradPlan {
+  int kind, tn, tk, tiles, nsplit, rows, groups;
+};
+ConvWgradPlan conv_wgrad_plan(int M, int N, int K, const ConvGeo& g, bool pro, bool db = false);
 // workspace of launch_conv_wgrad for this geometry (the 3x3 patch kernel's plan where it applies)
 int64_t conv_wgrad_ws_geo(int M, int N, int K, const ConvGeo& g, bool pro);
 bool conv_wgrad_is_wide(int M, int N, int K, int C, bool pro);

@@ -280,11 +280,15 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
   // kEpiFoldAddMaskedDs keeps its third running sum in LDS (8 floats per thread past the output tile): in
   // registers it pushed the register-staged variant from 20 to 76 B/lane of scratch
   constexpr int RED_ELEMS = 4 * NSUM * BN * 2 > (FOLD_DS ? 256 * 8 * 2 : 0) ? 4 * NSUM * BN * 2 : 256 * 8 * 2;
-  constexpr int EPI_ELEMS = BM * CS + RED_ELEMS;
   constexpr bool PATCH = VAR == 1;
   constexpr int NST = 2;  // LDS-DMA ring depth
   static_assert(VAR == 0 || VAR == 1, "plain or patch");
   constexpr int A_ELEMS = PATCH ? patch_bytes<BN>() / 2 : (TWO_GLDS ? 3 : NST) * BM * kBK;
+  // the third sum lives across stages and tiles, so its slots must lie past the stage buffers as well as
+  // past the output tile: with 64-channel tiles the output tile (128 x 68) ends inside stage buffer A1,
+  // whose staging writes overwrote the sum (128-channel tiles: 128 x 132 already ends past both buffers)
+  constexpr int S3_BASE = FOLD_DS && A_ELEMS > BM * CS ? A_ELEMS : BM * CS;
+  constexpr int EPI_ELEMS = S3_BASE + RED_ELEMS;
   constexpr int Z_BASE = 2 * BM * kBK;  // TWO_GLDS: the second source's stage tile
   constexpr int B_BASE = ((A_ELEMS > EPI_ELEMS ? A_ELEMS : EPI_ELEMS) + 7) & ~7;
   constexpr int LDS_ELEMS = B_BASE + NST * BN * kBK;
@@ -469,7 +473,7 @@ __device__ __forceinline__ void conv_fwd_body(const ConvGemmArgs& p, int GM, int
   float s1[8], s2[8], e0[8], e1[8], e2[8], e3[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = e0[j] = e1[j] = e2[j] = e3[j] = 0.f;
-  float* s3l = reinterpret_cast<float*>(lds + BM * CS) + t * 8;  // FOLD_DS: this thread's third sum
+  float* s3l = reinterpret_cast<float*>(lds + S3_BASE) + t * 8;  // FOLD_DS: this thread's third sum
   if constexpr (FOLD_DS) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) s3l[j] = 0.f;
@@ -1841,6 +1845,21 @@ bool conv_fwd_runs(const ConvFwdPlan& pl, int pro, int epi) {
   return true;
 }
 
+// The kernel family launch_conv_fwd runs for a plan: the ONE decision of its ladder (the launcher below
+// branches on this value and on nothing else, and the conv_gemm_family binding reports it to the tests).
+int conv_fwd_family(const ConvFwdPlan& pl, int M, int N, int K, const ConvGeo& g, int pro, int epi) {
+  const int src2 = pro_src2(pro);
+  if (pl.bm == 256 && pl.bn == 256) return kFamBig;
+  if (twosrc_glds(K, src2)) return kFamTwosrcGlds;  // (1x1: the binding checks)
+  // the 3x3 patch-staged tiles; the other epilogues run the im2col ladders
+  if (pro == kProNone && patch_fwd_ok(g, N, false) && (epi_is_fwd(epi) || epi == kEpiMaskSums)) return kFamPatch;
+  if (pl.bm == 256) return kFamTall;  // LDS-DMA only (no prologue, deep K)
+  if (src2 != kSrc2None) return kFamTwosrcReg;  // the register-staged two-source prologues (1x1, shallow K)
+  // deep K without a prologue: LDS-DMA staging (one tile per block)
+  if (pro == kProNone && pl.gm == (M + pl.bm - 1) / pl.bm && K / kBK > 2) return kFamGlds;
+  return kFamReg;
+}
+
 void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
   if (a0.M <= 0) return;
   ConvGemmArgs a = a0;
@@ -1852,7 +1871,8 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
   if (!conv_fwd_runs(pl, pro, a.epi)) conv_no_kernel(pro, a.epi);
   const int GM = pl.gm;
   const int nblk = GM * (a.N / pl.bn);
-  if (pl.bm == 256 && pl.bn == 256) {
+  const int fam = conv_fwd_family(pl, a.M, a.N, a.K, a.g, pro, a.epi);
+  if (fam == kFamBig) {
     launch_conv_big(a, s);
     return;
   }
@@ -1864,7 +1884,7 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
     switch (a.epi) { EPIS(L, 64, __VA_ARGS__) default: conv_no_kernel(pro, a.epi); }      \
   }
 #define PSAMD_EPIS_MASKSUMS(L, ...) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__)
-  if (twosrc_glds(a.K, src2)) {  // (1x1: the binding checks)
+  if (fam == kFamTwosrcGlds) {
 #define PSAMD_CF2S(BN, PRO, EPI) \
   hipLaunchKernelGGL((conv_fwd_kernel<128, BN, PRO, EPI, true, true>), dim3(nblk), dim3(256), 0, s, a, GM)
     if (resp) {
@@ -1875,8 +1895,7 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
 #undef PSAMD_CF2S
     return;
   }
-  // the 3x3 patch-staged tiles; the other epilogues run the im2col ladders below
-  if (pro == kProNone && patch_fwd_ok(a.g, a.N, false) && (epi_is_fwd(a.epi) || a.epi == kEpiMaskSums)) {
+  if (fam == kFamPatch) {
 #define PSAMD_EPIS_PATCH(L, ...)                                                              \
   PSAMD_EPI_CASE(L, kEpiStats, __VA_ARGS__) PSAMD_EPI_CASE(L, kEpiMaskSums, __VA_ARGS__)      \
   PSAMD_EPI_CASE(L, kEpiStore, __VA_ARGS__)
@@ -1888,8 +1907,7 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
     return;
   }
   const bool ks1 = a.g.ks == 1 && a.g.ksw <= 1;
-  // deep K without the BN prologue: LDS-DMA staging (one tile per block)
-  const bool glds = !a.pro && !bwd && pl.gm == (a.M + pl.bm - 1) / pl.bm && a.K / kBK > 2;
+  const bool glds = fam == kFamGlds;
 #define PSAMD_CF3(BM, BN, PRO, EPI, GL)                                                                          \
   if (ks1) hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, PRO, EPI, true, GL>), dim3(nblk), dim3(256), 0, s, a, GM); \
   else hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, PRO, EPI, false, GL>), dim3(nblk), dim3(256), 0, s, a, GM)
@@ -1897,13 +1915,13 @@ void launch_conv_fwd(const ConvGemmArgs& a0, hipStream_t s) {
   if constexpr (PRO != kProNone) { PSAMD_CF3(128, BN, PRO, EPI, false); } \
   else if (glds) { PSAMD_CF3(128, BN, PRO, EPI, true); }                  \
   else { PSAMD_CF3(128, BN, PRO, EPI, false); }
-  if (pl.bm == 256) {  // LDS-DMA only (no prologue, deep K)
+  if (fam == kFamTall) {
 #define PSAMD_CFT(BN, EPI) PSAMD_CF3(256, BN, kProNone, EPI, true)
     switch (a.epi) { PSAMD_EPIS_NO_DS(PSAMD_CFT, 64) default: conv_no_kernel(pro, a.epi); }
 #undef PSAMD_CFT
     return;
   }
-  if (resp || bwd) {  // the register-staged two-source prologues (1x1, shallow K)
+  if (fam == kFamTwosrcReg) {
 #define PSAMD_CFR(BN, PRO, EPI) \
   hipLaunchKernelGGL((conv_fwd_kernel<128, BN, PRO, EPI, true, false>), dim3(nblk), dim3(256), 0, s, a, GM)
     if (resp) {  // forward over the previous block's output, applied while staging
@@ -2076,11 +2094,23 @@ void slab_reduce(const ConvWgradArgs& a, int nsplit, int groups, hipStream_t s) 
 bool conv_wgrad_patch_ok(const ConvGeo& g, int M, int N, bool pro) { return patch_ok(g, M, N, pro); }
 
 int64_t conv_wgrad_ws_geo(int M, int N, int K, const ConvGeo& g, bool pro) {
-  if (patch_ok(g, M, N, pro)) {
+  const ConvWgradPlan w = conv_wgrad_plan(M, N, K, g, pro, false);
+  return static_cast<int64_t>(w.nsplit + w.groups) * N * K;
+}
+
+// The ONE plan of a weight gradient: launch_conv_wgrad and conv_wgrad_ws_geo consume it, the binding
+// reports it.  db: the launch also sums dz's columns (wide kernel only; no patch kernel then).
+ConvWgradPlan conv_wgrad_plan(int M, int N, int K, const ConvGeo& g, bool pro, bool db) {
+  if (!db && patch_ok(g, M, N, pro)) {
     const PPlan w = pplan(g, M, N);
-    return static_cast<int64_t>(w.nsplit + w.groups) * N * K;
+    return ConvWgradPlan{5, 64, 64, w.tiles, w.nsplit, w.spp, w.groups};
   }
-  return conv_wgrad_ws(M, N, K, g.C, pro);
+  const WPlan w = wplan(M, N, K, g.C, pro);
+  if (w.wide) {
+    const int bno = w.wide <= 2 ? 256 : 128, bko = w.wide == 1 || w.wide == 3 ? 256 : w.wide == 2 ? 128 : 384;
+    return ConvWgradPlan{w.wide, bno, bko, w.tiles, w.nsplit, w.rows, w.groups};
+  }
+  return ConvWgradPlan{0, 64 * w.tno, 64 * w.tko, w.tiles, w.nsplit, w.rows, w.groups};
 }
 
 int conv_wgrad_splits(int M, int N, int K, int C, bool pro) { return wplan(M, N, K, C, pro).nsplit; }
@@ -2096,17 +2126,15 @@ void launch_conv_wgrad(const ConvWgradArgs& a0, hipStream_t s) {
   ConvWgradArgs a = a0;
   a.fd_ohw = make_fastdiv(static_cast<uint32_t>(a.g.OH * a.g.OW));
   a.fd_ow = make_fastdiv(static_cast<uint32_t>(a.g.OW));
-  if (a.db == nullptr && patch_ok(a.g, a.M, a.N, a.pro != nullptr)) {
-    const PPlan w = pplan(a.g, a.M, a.N);
-    const int nblk = w.tiles * w.nsplit;
-    if (a.g.stride == 2) hipLaunchKernelGGL((conv_wgrad_patch_kernel<56, 2>), dim3(nblk), dim3(768), 0, s, a, w.spp);
-    else if (a.g.W == 56) hipLaunchKernelGGL((conv_wgrad_patch_kernel<56, 1>), dim3(nblk), dim3(768), 0, s, a, w.spp);
-    else hipLaunchKernelGGL((conv_wgrad_patch_kernel<28, 1>), dim3(nblk), dim3(768), 0, s, a, w.spp);
+  const ConvWgradPlan w = conv_wgrad_plan(a.M, a.N, a.K, a.g, a.pro != nullptr, a.db != nullptr);
+  const int nblk = w.tiles * w.nsplit;
+  if (w.kind == 5) {  // rows: 112-pixel stages per split
+    if (a.g.stride == 2) hipLaunchKernelGGL((conv_wgrad_patch_kernel<56, 2>), dim3(nblk), dim3(768), 0, s, a, w.rows);
+    else if (a.g.W == 56) hipLaunchKernelGGL((conv_wgrad_patch_kernel<56, 1>), dim3(nblk), dim3(768), 0, s, a, w.rows);
+    else hipLaunchKernelGGL((conv_wgrad_patch_kernel<28, 1>), dim3(nblk), dim3(768), 0, s, a, w.rows);
     slab_reduce(a, w.nsplit, w.groups, s);
     return;
   }
-  const WPlan w = wplan(a.M, a.N, a.K, a.g.C, a.pro != nullptr);
-  const int nblk = w.tiles * w.nsplit;
   // LIN: 1x1 stride-1 pad-0 geometry (X row m = pixel m), DMA sources without the pixel decode
   const bool lin = a.g.ks == 1 && a.g.stride == 1 && a.g.pad == 0;
   const bool prol = a.g.ks == 1;  // the LDS pass maps k to the channel directly
@@ -2128,24 +2156,24 @@ void launch_conv_wgrad(const ConvWgradArgs& a0, hipStream_t s) {
   // without the prologue both operands are plain row slices: LDS-DMA staging
 #define PSAMD_CWP(TN, TK) \
   if (a.pro) { PSAMD_CW(TN, TK, true, false); } else { PSAMD_CW(TN, TK, false, true); }
-  if (w.wide == 1) {
+  if (w.kind == 1) {
     PSAMD_CWW(2, 4, 4, 2);
-  } else if (w.wide == 2) {
+  } else if (w.kind == 2) {
     PSAMD_CWW(2, 2, 4, 2);
-  } else if (w.wide == 3) {
+  } else if (w.kind == 3) {
     PSAMD_CWW(2, 2, 2, 4);
-  } else if (w.wide == 4) {
+  } else if (w.kind == 4) {
     PSAMD_CWW(2, 3, 2, 4);
-  } else if (w.tno == 2) {
-    if (w.tko == 2) { PSAMD_CWP(2, 2) } else { PSAMD_CWP(2, 1) }
+  } else if (w.tn == 128) {
+    if (w.tk == 128) { PSAMD_CWP(2, 2) } else { PSAMD_CWP(2, 1) }
   } else {
-    if (w.tko == 2) { PSAMD_CWP(1, 2) } else { PSAMD_CWP(1, 1) }
+    if (w.tk == 128) { PSAMD_CWP(1, 2) } else { PSAMD_CWP(1, 1) }
   }
 #undef PSAMD_CWW
 #undef PSAMD_CWW3
 #undef PSAMD_CWP
 #undef PSAMD_CW
-  if (w.wide && a.db != nullptr && a.pro == nullptr)  // bias gradient: fold the per-split column sums
+  if (w.kind != 0 && a.db != nullptr && a.pro == nullptr)  // bias gradient: fold the per-split column sums
     hipLaunchKernelGGL(slab_reduce_kernel<false>, dim3((a.N + 255) / 256), dim3(256), 0, s, a.dbws, w.nsplit,
                        w.nsplit, static_cast<int64_t>(a.N), static_cast<void*>(a.db));
   slab_reduce(a, w.nsplit, w.groups, s);
