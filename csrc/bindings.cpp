@@ -931,22 +931,36 @@ static void check_attn(const Tensor& qkv, int64_t heads) {
   TORCH_CHECK(qkv.size(0) * heads < (int64_t(1) << 31), "batch * heads");
 }
 
-std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed) {
+// key_lengths (optional, int32 [B] on qkv's device): right-padded batch.  Only the layout is checked:
+// the kernels clamp every value to [1, S], so no value needs a look (that would be a host sync)
+static const int32_t* attn_klen(const c10::optional<Tensor>& key_lengths, const Tensor& qkv) {
+  if (!key_lengths.has_value()) return nullptr;
+  const Tensor& k = *key_lengths;
+  TORCH_CHECK(k.device() == qkv.device(), "key_lengths on qkv's device");
+  TORCH_CHECK(k.scalar_type() == torch::kInt32 && k.is_contiguous() && k.numel() == qkv.size(0),
+              "key_lengths int32, contiguous, one per batch row");
+  return k.data_ptr<int32_t>();
+}
+
+std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths) {
   check_attn(qkv, heads);
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p in [0, 1)");
   const int64_t B = qkv.size(0), S = qkv.size(1);
+  const int32_t* klen = attn_klen(key_lengths, qkv);
   const c10::DeviceGuard guard(qkv.device());
   auto out = torch::empty({B, S, heads * 64}, qkv.options());
   auto lse = torch::empty({B, heads, S}, qkv.options().dtype(torch::kFloat32));
   psamd::launch_attn_fwd(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(S),
                          static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed),
-                         cur_stream(qkv));
+                         cur_stream(qkv), klen);
   return {out, lse};
 }
 
-Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed) {
+Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed,
+                c10::optional<Tensor> key_lengths) {
   check_attn(qkv, heads);
   const int64_t B = qkv.size(0), S = qkv.size(1);
+  const int32_t* klen = attn_klen(key_lengths, qkv);
   check_rows(out, "out");
   check_rows(dout, "dout");
   TORCH_CHECK(out.sizes() == torch::IntArrayRef({B, S, heads * 64}) && dout.sizes() == out.sizes(),
@@ -958,7 +972,7 @@ Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, 
   auto dqkv = torch::empty_like(qkv);
   psamd::launch_attn_bwd(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B),
                          static_cast<int>(S), static_cast<int>(heads), 0.125f, static_cast<float>(p),
-                         static_cast<uint64_t>(seed), cur_stream(qkv));
+                         static_cast<uint64_t>(seed), cur_stream(qkv), klen);
   return dqkv;
 }
 
@@ -2118,13 +2132,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
+        py::arg("key_lengths") = py::none());
   m.def("xent_fwd", &xent_fwd, py::arg("x"), py::arg("labels"), py::arg("ignore_index"));
   m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("go"), py::arg("count"),
         py::arg("ignore_index"));
   m.def("fa_fwd", &fa_fwd);
   m.def("fa_bwd", &fa_bwd);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("heads"),
+        py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none());
   m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -36,6 +36,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kD = 64;    // head dim
 constexpr int kS = 128;   // max sequence length
 constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kMasked = -3.0e38f;  // score of a pad key (the running max starts there too)
 
 // 128-B rows (RL 64): chunk ^ f(row pair), f(p) = ((p & 1) << 2) | (p >> 1) on p = (r >> 1) & 7
 // 256-B rows (RL 128): chunk ^ (((r & 3) << 2) | ((r >> 2) & 3))
@@ -110,12 +111,12 @@ __device__ __forceinline__ bf16x8_t p_operand(const f32x16& blk, int s, int hl) 
   return __builtin_bit_cast(bf16x8_t, u32x4{a[0], b[0], a[1], b[1]});
 }
 
-// stage rows [0, S) of N heads' 64-wide slices (row strides rs[i] elements) into [128][64] tiles,
-// rows S..127 zeroed; 256 threads: every chunk's global load is issued before any LDS store (a
-// load-store loop paid one HBM round trip per 4 KiB: the kernels ran at ~2.4 TB/s)
+// stage rows [0, nr[i]) of N heads' 64-wide slices (row strides rs[i] elements) into [128][64] tiles,
+// rows nr[i]..127 zeroed (and not read); 256 threads: every chunk's global load is issued before any
+// LDS store (a load-store loop paid one HBM round trip per 4 KiB: the kernels ran at ~2.4 TB/s)
 template <int N>
 __device__ __forceinline__ void stage64n(uint16_t* const (&T)[N], const uint16_t* const (&src)[N],
-                                         const int64_t (&rs)[N], int S) {
+                                         const int64_t (&rs)[N], const int (&nr)[N]) {
   constexpr int PER = kS * 8 / 256;  // 16-B chunks per thread per tile
   u16x8 v[N][PER];
 #pragma unroll
@@ -124,7 +125,7 @@ __device__ __forceinline__ void stage64n(uint16_t* const (&T)[N], const uint16_t
     for (int i = 0; i < PER; ++i) {
       const int id = threadIdx.x + i * 256, r = id >> 3, ch = id & 7;
       v[n][i] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (r < S) v[n][i] = *reinterpret_cast<const u16x8*>(src[n] + r * rs[n] + ch * 8);
+      if (r < nr[n]) v[n][i] = *reinterpret_cast<const u16x8*>(src[n] + r * rs[n] + ch * 8);
     }
 #pragma unroll
   for (int n = 0; n < N; ++n)
@@ -136,15 +137,30 @@ __device__ __forceinline__ void stage64n(uint16_t* const (&T)[N], const uint16_t
 }
 
 
+// Right-padded batches (LEN): sequence b has L = clamp(klen[b], 1, S) valid keys (block-uniform, any
+// int32 is safe).  Keys >= L take no part in any softmax -- SDPA with a key-padding mask; all S query
+// rows stay ordinary rows, and the dropout element indices do not change.  K / V rows >= L are
+// staged as zeros and not read, whole 32-key blocks beyond L are skipped, and in the partly valid
+// block the pad keys are excluded by SELECT (a pad row may hold any finite value, one whose score
+// overflows exp2 included).  LEN = false is the unpadded kernel, unchanged.
+//
+// is accumulator element e of key block kb, on lane half hl, a key below L
+__device__ __forceinline__ bool key_ok(int kb, int e, int hl, int L) {
+  return kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hl < L;
+}
+
 // ------------------------------------------------------------------------------ forward
-template <bool DROP>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
-                                                       float* __restrict__ lse, int S, int H, float scale,
-                                                       uint64_t seed, uint32_t thr, float rkeep) {
+// (LEN asks for 3 blocks per CU: without the hint the allocator ends 2 VGPRs above that step)
+template <bool DROP, bool LEN>
+__global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
+    const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse, int S, int H, float scale,
+    uint64_t seed, uint32_t thr, float rkeep, const int32_t* __restrict__ klen) {
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[kS * kD];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hl = lane >> 5, c = lane & 31;
+  int L = S;  // key bound
+  if constexpr (LEN) L = min(max(klen[b], 1), S);
   const int64_t rs = 3LL * H * kD;
   const uint16_t* base = qkv + static_cast<int64_t>(b) * S * rs + h * kD;
   const int q0 = w * 32;
@@ -158,11 +174,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
     uint16_t* const tt[2] = {Ks, Vs};
     const uint16_t* const ss[2] = {base + H * kD, base + 2 * H * kD};
     const int64_t rr[2] = {rs, rs};
-    stage64n<2>(tt, ss, rr, S);
+    const int nr[2] = {L, L};
+    stage64n<2>(tt, ss, rr, nr);
   }
   __syncthreads();
   if (q0 >= S) return;  // no barrier below
-  const int nkb = S >> 5;
+  const int nkb = LEN ? (L + 31) >> 5 : S >> 5;
   f32x16 st[4];
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb) {
@@ -181,7 +198,11 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
   for (int kb = 0; kb < 4; ++kb)
     if (kb < nkb)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) m = fmaxf(m, st[kb][e]);
+      for (int e = 0; e < 16; ++e) {
+        // a pad key's score by select: out of the max, and its p = exp2(-huge) is 0 exactly
+        if constexpr (LEN) st[kb][e] = key_ok(kb, e, hl, L) ? st[kb][e] : kMasked;
+        m = fmaxf(m, st[kb][e]);
+      }
   {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
     m = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
@@ -208,6 +229,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
   for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
     for (int e = 0; e < 16; e += 2) {
+      if constexpr (LEN)
+        if (kb >= nkb) continue;  // a skipped block: its p are zeros already, no hash
       float p0 = st[kb][e] * inv, p1 = st[kb][e + 1] * inv;
       if constexpr (DROP) {  // keys key, key + 1 (key even): one hash
         const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hl;
@@ -246,11 +269,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restric
 }
 
 // ------------------------------------------------------------------------------ backward
-template <bool DROP>
+// LEN: K is staged with the key bound L (Q and dO are query-indexed: bound S); P, P_drop and dS of
+// keys >= L are zeros by select -- the V fragments come straight from global memory, pad rows
+// included -- so dK / dV rows [L, S) are exact zeros: a key wave at or beyond L stores them without
+// running its GEMMs, the pad keys inside the partly valid block get them from the zero columns of T.
+template <bool DROP, bool LEN>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                        const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                        uint16_t* __restrict__ dqkv, int S, int H, float scale,
-                                                       uint64_t seed, uint32_t thr, float rkeep) {
+                                                       uint64_t seed, uint32_t thr, float rkeep,
+                                                       const int32_t* __restrict__ klen) {
   __shared__ __attribute__((aligned(16))) uint16_t Qs[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t dOs[kS * kD];
@@ -264,6 +292,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
   uint16_t* gbase = dqkv + static_cast<int64_t>(b) * S * rs + h * kD;
   const int q0 = w * 32, q = q0 + c;
   const bool act = q0 < S;  // wave-uniform
+  int L = S;  // key bound
+  if constexpr (LEN) L = min(max(klen[b], 1), S);
   // this lane's O / dO row halves and the row's log-sum-exp, loaded before the staging so their
   // latency overlaps it (Dq = rowsum(dO * O) is formed after the barrier)
   const int qq = min(q, S - 1);
@@ -278,10 +308,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
     uint16_t* const tt[3] = {Qs, Ks, dOs};
     const uint16_t* const ss[3] = {base, base + H * kD, dobase};
     const int64_t rr[3] = {rs, rs, ors};
-    stage64n<3>(tt, ss, rr, S);
+    const int nr[3] = {S, L, S};
+    stage64n<3>(tt, ss, rr, nr);
   }
   __syncthreads();
-  const int nkb = S >> 5;
+  const int nkb = LEN ? (L + 31) >> 5 : S >> 5;
   float dd = 0.f;  // formed right away: the row registers die before the MFMA accumulators live
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -309,6 +340,14 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
               *reinterpret_cast<const bf16x8_t*>(base + 2 * H * kD + (kb * 32 + c) * rs + 16 * s + 8 * hl);
           ds[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, of[s], ds[kb], 0, 0, 0);
         }
+        if constexpr (LEN) {  // pad keys: p = exp2(-huge) = 0 exactly, and dp = 0 whatever the V row holds
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const bool ok = key_ok(kb, e, hl, L);
+            pt[kb][e] = ok ? pt[kb][e] : kMasked;
+            ds[kb][e] = ok ? ds[kb][e] : 0.f;
+          }
+        }
       }
     }
     // Dq = rowsum(dO * O) for query q: this lane's half of the 64 d, then the other half
@@ -318,6 +357,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int e = 0; e < 16; e += 2) {
+        if constexpr (LEN)
+          if (kb >= nkb) continue;  // a skipped block: pt and ds are zeros already, no hash
         uint32_t hh = 0;
         if constexpr (DROP) {  // keys key, key + 1 (key even): one hash
           const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hl;
@@ -354,9 +395,17 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
   put(pt);
   __syncthreads();
   const int k0 = w * 32;
-  const bool kact = k0 < S;
+  const bool kact = LEN ? k0 < L : k0 < S;
   const int nqs = S >> 4;  // 16-query steps
   uint16_t* krow = gbase + static_cast<int64_t>(k0 + c) * rs;
+  if constexpr (LEN) {
+    if (k0 >= L && k0 < S) {  // a fully padded key wave: dK = dV = 0 (dqkv is not pre-zeroed)
+#pragma unroll
+      for (int t = 1; t < 3; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) *reinterpret_cast<u16x4*>(krow + t * H * kD + 8 * j + 4 * hl) = u16x4{0, 0, 0, 0};
+    }
+  }
   auto store_t = [&](const f32x16 (&acc)[2], uint16_t* row, float mul) {
     // acc^T layout: lane column = key (or query) row of the output, rows d: 8-B pieces
 #pragma unroll
@@ -427,26 +476,25 @@ __global__ void attn_dropout_mask_kernel(uint8_t* __restrict__ mask, int64_t n, 
 
 }  // namespace
 
+// klen == nullptr: the unpadded (LEN = false) kernels
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int S, int H, float scale, float p,
-                     uint64_t seed, hipStream_t s) {
+                     uint64_t seed, hipStream_t s, const int32_t* klen) {
   const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 65536.0 + 0.5);
   const float rkeep = thr > 0 ? static_cast<float>(65536.0 / (65536.0 - thr)) : 1.f;  // 1 / (1 - p_eff)
   const dim3 grid(B * H);
-  if (p > 0.f) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, s, qkv, out, lse, S, H, scale, seed, thr, rkeep);
-  else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, s, qkv, out, lse, S, H, scale, seed, thr, rkeep);
+  auto* k = p > 0.f ? (klen ? attn_fwd_kernel<true, true> : attn_fwd_kernel<true, false>)
+                    : (klen ? attn_fwd_kernel<false, true> : attn_fwd_kernel<false, false>);
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, lse, S, H, scale, seed, thr, rkeep, klen);
 }
 
 void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, uint16_t* dqkv,
-                     int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s) {
+                     int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s, const int32_t* klen) {
   const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 65536.0 + 0.5);
   const float rkeep = thr > 0 ? static_cast<float>(65536.0 / (65536.0 - thr)) : 1.f;  // 1 / (1 - p_eff)
   const dim3 grid(B * H);
-  if (p > 0.f)
-    hipLaunchKernelGGL(attn_bwd_kernel<true>, grid, dim3(256), 0, s, qkv, out, dout, lse, dqkv, S, H, scale, seed, thr,
-                       rkeep);
-  else
-    hipLaunchKernelGGL(attn_bwd_kernel<false>, grid, dim3(256), 0, s, qkv, out, dout, lse, dqkv, S, H, scale, seed,
-                       thr, rkeep);
+  auto* k = p > 0.f ? (klen ? attn_bwd_kernel<true, true> : attn_bwd_kernel<true, false>)
+                    : (klen ? attn_bwd_kernel<false, true> : attn_bwd_kernel<false, false>);
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, dout, lse, dqkv, S, H, scale, seed, thr, rkeep, klen);
 }
 
 void launch_attn_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, hipStream_t s) {

@@ -5,7 +5,8 @@ Compact in-repo definitions (transformers is not needed on the hot path): parame
 and counts match the published architectures -- BERT-base 110M (12 x 768, 12 heads, FFN
 3072, vocab 30522), Llama-3-8B 8.03B (32 x 4096, 32 q / 8 kv heads, FFN 14336, vocab
 128256, RoPE theta 500000).  BERT attention (S <= 128) runs the fused MFMA kernel of
-csrc/kernels/attention.hip, Llama's causal GQA attention the flash kernel of flash_attn.hip;
+csrc/kernels/attention.hip (right-padded batches too: ``BertForMLM.forward(..., lengths=)``,
+``mlm_batch(..., lengths=)``), Llama's causal GQA attention the flash kernel of flash_attn.hip;
 everything is bf16 on the GPU with fp32 masters on the parameter-server shards.
 """
 from __future__ import annotations
@@ -51,12 +52,13 @@ class BertLayer(nn.Module):
         self.fc2 = SplitKLinear(c.ffn, c.hidden)
         self.ln2 = nn.LayerNorm(c.hidden, eps=c.eps)
 
-    def forward(self, x, mask: Optional[torch.Tensor] = None):
+    def forward(self, x, mask: Optional[torch.Tensor] = None, key_lengths: Optional[torch.Tensor] = None):
         p = self.c.dropout if self.training else 0.0
-        # fused MFMA attention over the qkv projection for S <= 128 (ops/transformer.py), SDPA else
+        # fused MFMA attention over the qkv projection for S <= 128 (ops/transformer.py), SDPA else;
+        # key_lengths [B] (a right-padded batch) stays on the fused kernel, an arbitrary mask does not
         # fork: x's residual gradient is added inside the qkv / fc1 data-gradient GEMM (ops/dense.py)
         qkv, xr = self.qkv.fork(x)
-        a = attention_qkv(qkv, self.c.heads, p, mask)
+        a = attention_qkv(qkv, self.c.heads, p, mask, key_lengths)
         # post-LN epilogues: LN(x + dropout(sublayer)) as one fused HIP pass each way
         x = layer_norm_residual(xr, self.proj(a), self.ln1.weight, self.ln1.bias, self.c.eps, p, self.training)
         h, xr = self.fc1.fork(x)
@@ -87,17 +89,26 @@ class BertForMLM(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
-    def forward(self, ids, labels=None, positions=None):
+    def forward(self, ids, labels=None, positions=None, lengths=None):
         """``positions`` [B, P] (the masked-LM positions of the original BERT pretraining input
         format, ``masked_lm_positions``): the LM head runs only on those B*P rows -- the vocab
         projection and its softmax are 1/(S/P) of the dense-head cost.  Without positions the
-        head runs on every token (labels -100 are ignored)."""
+        head runs on every token (labels -100 are ignored).
+
+        ``lengths`` [B] (any integer dtype): a right-padded batch -- tokens at or beyond
+        ``lengths[b]`` of sequence b are padding that no token attends to (key lengths of every
+        layer's attention); their labels should be -100 (``mlm_batch(..., lengths=)``)."""
         b, s = ids.shape
         pos = torch.arange(s, device=ids.device)
         x = self.word(ids) + self.pos(pos)[None] + self.tok_type.weight[0]
         x = F.dropout(self.ln(x), self.c.dropout, self.training)
-        for layer in self.layers:
-            x = layer(x)
+        if lengths is None:
+            for layer in self.layers:
+                x = layer(x)
+        else:  # converted once: every layer gets the int32 device tensor the kernel reads
+            klen = torch.as_tensor(lengths).to(device=ids.device, dtype=torch.int32, non_blocking=True)
+            for layer in self.layers:
+                x = layer(x, key_lengths=klen)
         if positions is not None:
             flat = (positions + torch.arange(b, device=ids.device)[:, None] * s).reshape(-1)
             x = x.reshape(b * s, -1).index_select(0, flat)
@@ -110,13 +121,50 @@ class BertForMLM(nn.Module):
         return cross_entropy(logits.view(-1, self.c.vocab), labels.reshape(-1), ignore_index=-100)
 
 
+def _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions):
+    """mlm_batch for a right-padded batch: ``ids`` are the full-length draws, ``g`` their generator."""
+    batch, seq = ids.shape
+    lens = torch.as_tensor(lengths, dtype=torch.int64).cpu()
+    lens = lens.expand(batch).clone() if lens.dim() == 0 else lens
+    if lens.shape != (batch,) or int(lens.min()) < 1 or int(lens.max()) > seq:
+        raise ValueError("mlm_batch: lengths is an int or [batch] integers in [1, seq]")
+    npred = torch.tensor([max(1, int(round(mask_prob * n))) for n in lens.tolist()])  # <= length
+    cols = torch.arange(seq)[None, :]
+    pad = cols >= lens[:, None]
+    # a random order of each sequence's valid positions, its pad positions behind them
+    order = torch.rand(batch, seq, generator=g).masked_fill(pad, 2.0).argsort(dim=1)
+    P = int(npred.max())
+    real = torch.arange(P)[None, :] < npred[:, None]  # [B, P]: a masked position, not a filler
+    chosen = torch.zeros(batch, seq, dtype=torch.bool).scatter_(1, order[:, :P], real)
+    # the filler: the next position of the order -- valid and unmasked, or (all of the sequence is
+    # masked) a pad position; a row that needs a filler has npred < P <= seq, so the index exists
+    filler = order.gather(1, npred.clamp(max=seq - 1)[:, None])
+    positions = order[:, :P].masked_fill(~real, seq).sort(dim=1).values  # masked ones ascending, first
+    positions = torch.where(positions < seq, positions, filler)
+    labels = torch.where(chosen, ids, torch.full_like(ids, -100))
+    ids = ids.masked_fill(chosen, 103).masked_fill(pad, 0)  # [MASK], [PAD]
+    if device is not None:
+        ids, labels, positions, lens = ids.to(device), labels.to(device), positions.to(device), lens.to(device)
+    return (ids, labels, positions, lens) if with_positions else (ids, labels, lens)
+
+
 def mlm_batch(batch: int, seq: int, vocab: int = 30522, mask_prob: float = 0.15, seed: int = 0, device=None,
-              with_positions: bool = False):
+              with_positions: bool = False, lengths=None):
     """Synthetic MLM batch in the BERT pretraining format: exactly round(mask_prob * seq)
     masked positions per sequence (create_pretraining_data's num_to_predict), replaced by
-    [MASK]; labels -100 elsewhere.  ``with_positions`` also returns masked_lm_positions [B, P]."""
+    [MASK]; labels -100 elsewhere.  ``with_positions`` also returns masked_lm_positions [B, P].
+
+    ``lengths`` (an int, or [batch] integers in [1, seq]) makes a right-padded batch and is returned
+    last, as an int64 tensor: positions >= length hold id 0 ([PAD]) and label -100, and sequence b
+    masks max(1, round(mask_prob * length_b)) positions of [0, length_b).  ``positions`` stays
+    rectangular at the batch maximum count: a shorter row is filled by repeating one of its valid
+    unmasked positions (label -100, so the head ignores it; a sequence masked in full, such as one
+    of length 1, repeats a pad position instead).  Without ``lengths`` the batch is what it always
+    was for the seed."""
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(min(1000, vocab // 2), vocab, (batch, seq), generator=g)
+    if lengths is not None:
+        return _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions)
     npred = max(1, int(round(mask_prob * seq)))
     positions = torch.rand(batch, seq, generator=g).argsort(dim=1)[:, :npred].sort(dim=1).values
     labels = torch.full_like(ids, -100)

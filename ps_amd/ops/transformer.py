@@ -4,8 +4,9 @@
   layer_norm_residual(x, o, g, b, eps, p)    -> LN(x + dropout_p(o))        (BERT post-LN)
   swiglu(gu)                                  -> silu(gu[..., :F]) * gu[..., F:]
   rope_split(qkv, cs, H, KV)                  -> q, k, v  (RoPE + head split + transpose)
-  attention_qkv(qkv, H, p, mask)              -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
-                                                 projection (csrc/kernels/attention.hip, S <= 128)
+  attention_qkv(qkv, H, p, mask, key_lengths) -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
+                                                 projection (csrc/kernels/attention.hip, S <= 128;
+                                                 right-padded batches by per-sequence key_lengths)
   attention_causal_gqa(q, k, v)               -> causal GQA flash attention, heads merged
                                                  (csrc/kernels/flash_attn.hip, head dim 128)
 
@@ -176,7 +177,8 @@ def rope_split(qkv: torch.Tensor, cs: torch.Tensor, H: int, KV: int):
 
 # ------------------------------------------------------------------------------ attention
 def attention_qkv_ok(qkv: torch.Tensor, heads: int, mask) -> bool:
-    """The fused kernel's domain: GPU bf16, head dim 64, S a multiple of 32 up to 128, no mask."""
+    """The fused kernel's domain: GPU bf16, head dim 64, S a multiple of 32 up to 128, no mask
+    (a right-padded batch is given by key lengths, not by a mask: attention_qkv)."""
     return (mask is None and _hip(qkv) and qkv.dim() == 3 and qkv.shape[2] == 3 * heads * 64
             and qkv.shape[1] % 32 == 0 and 0 < qkv.shape[1] <= 128
             and knobs.enabled("fused_attn"))
@@ -184,27 +186,67 @@ def attention_qkv_ok(qkv: torch.Tensor, heads: int, mask) -> bool:
 
 class _FusedAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p):
+    def forward(ctx, qkv, heads, p, key_lengths):
         qkv = qkv.contiguous()
         seed = _seed() if p > 0 else 0
-        out, lse = native().attn_fwd(qkv, heads, float(p), seed)
-        ctx.save_for_backward(qkv, out, lse)
+        if key_lengths is None:
+            out, lse = native().attn_fwd(qkv, heads, float(p), seed)
+            ctx.save_for_backward(qkv, out, lse)
+        else:
+            out, lse = native().attn_fwd(qkv, heads, float(p), seed, key_lengths)
+            ctx.save_for_backward(qkv, out, lse, key_lengths)
         ctx.heads, ctx.p, ctx.seed = heads, float(p), seed
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        return native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed), None, None
+        qkv, out, lse, *klen = ctx.saved_tensors
+        return native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, *klen), None, None, None
 
 
-def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+def key_lengths_from_mask(mask: torch.Tensor) -> torch.Tensor:
+    """Per-sequence key lengths [B] of a right-padded batch from its boolean token mask [B, S] (True:
+    a real token): ``mask.sum(1)``.  A CPU mask is checked to be a prefix mask (``ValueError``
+    otherwise: left padding and holes are not key lengths); a GPU mask is not looked at (no sync)."""
+    if mask.dim() != 2:
+        raise ValueError("key_lengths_from_mask: mask [B, S]")
+    m = mask.bool()
+    lengths = m.sum(1)
+    if not m.is_cuda:
+        prefix = torch.arange(m.shape[1], device=m.device)[None, :] < lengths[:, None]
+        if not torch.equal(m, prefix):
+            raise ValueError("key_lengths_from_mask: not a prefix (right-padding) mask")
+    return lengths
+
+
+def _device_key_lengths(key_lengths: torch.Tensor, qkv: torch.Tensor) -> torch.Tensor:
+    """[B] int32 on qkv's device, no sync (an int32 tensor already there passes through)."""
+    if key_lengths.dim() != 1 or key_lengths.shape[0] != qkv.shape[0]:
+        raise ValueError("key_lengths: one length per batch row, [B]")
+    if key_lengths.is_floating_point() or key_lengths.is_complex() or key_lengths.dtype == torch.bool:
+        raise ValueError("key_lengths: an integer tensor")
+    return key_lengths.to(device=qkv.device, dtype=torch.int32, non_blocking=True).contiguous()
+
+
+def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[torch.Tensor] = None,
+                  key_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Multi-head self-attention over the fused projection ``qkv`` [B, S, 3 * H * D] (q | k | v,
     heads inner) -> [B, S, H * D], dropout ``p`` on the probabilities.  On the fused kernel the
-    heads are never split into separate q / k / v tensors and the output is already merged."""
+    heads are never split into separate q / k / v tensors and the output is already merged.
+
+    ``key_lengths`` [B] (any integer dtype) describes a right-padded batch: keys at or beyond
+    ``clamp(key_lengths[b], 1, S)`` of sequence b take no part in any softmax, as under SDPA with a
+    key-padding mask; every query row, padded ones included, is an ordinary row.  It stays in the
+    fused kernel's domain.  An arbitrary ``mask`` goes to SDPA; giving both raises ``ValueError``."""
+    if key_lengths is not None and mask is not None:
+        raise ValueError("attention_qkv: give mask or key_lengths, not both")
     if attention_qkv_ok(qkv, heads, mask):
-        return _FusedAttention.apply(qkv, heads, float(p))
+        klen = None if key_lengths is None else _device_key_lengths(key_lengths, qkv)
+        return _FusedAttention.apply(qkv, heads, float(p), klen)
     b, s, _ = qkv.shape
+    if key_lengths is not None:
+        klen = _device_key_lengths(key_lengths, qkv).clamp(1, s)
+        mask = (torch.arange(s, device=qkv.device)[None, :] < klen[:, None])[:, None, None, :]  # [B, 1, 1, S]
     q, k, v = qkv.view(b, s, 3, heads, -1).permute(2, 0, 3, 1, 4)
     a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p)
     return a.transpose(1, 2).reshape(b, s, -1)
