@@ -1028,21 +1028,38 @@ Tensor xent_bwd(Tensor x, Tensor lab, Tensor lse, Tensor go, Tensor count, int64
   return dx;
 }
 
-std::vector<Tensor> fa_fwd(Tensor q, Tensor k, Tensor v) {
+// doc_start / doc_end (optional, int32 [B, S] on q's device): packed documents.  Only the layout is
+// checked: the kernels clamp every bound into the row, so no value needs a look (a host sync)
+static const int32_t* fa_bound(const c10::optional<Tensor>& bound, const Tensor& q, const char* name) {
+  if (!bound.has_value()) return nullptr;
+  const Tensor& t = *bound;
+  TORCH_CHECK(t.device() == q.device(), name, " on q's device");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous() && t.dim() == 2 && t.size(0) == q.size(0) &&
+                  t.size(1) == q.size(2),
+              name, " int32, contiguous, [B, S]");
+  return t.data_ptr<int32_t>();
+}
+
+std::vector<Tensor> fa_fwd(Tensor q, Tensor k, Tensor v, c10::optional<Tensor> doc_start) {
   check_fa(q, k, v);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  const int32_t* ds = fa_bound(doc_start, q, "doc_start");
   const c10::DeviceGuard guard(q.device());
   auto out = torch::empty({B, S, H * 128}, q.options());
   auto lse = torch::empty({B, H, S}, q.options().dtype(torch::kFloat32));
   psamd::launch_fa_fwd(u16(q), u16(k), u16(v), u16m(out), lse.data_ptr<float>(), static_cast<int>(B),
                        static_cast<int>(S), static_cast<int>(H), static_cast<int>(KV), 1.f / std::sqrt(128.f),
-                       cur_stream(q));
+                       cur_stream(q), ds);
   return {out, lse};
 }
 
-std::vector<Tensor> fa_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor lse) {
+std::vector<Tensor> fa_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor lse,
+                           c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end) {
   check_fa(q, k, v);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(), "fa_bwd: doc_start and doc_end, or neither");
+  const int32_t* ds = fa_bound(doc_start, q, "doc_start");
+  const int32_t* de = fa_bound(doc_end, q, "doc_end");
   check_rows(out, "out");
   check_rows(dout, "dout");
   TORCH_CHECK(out.numel() == B * S * H * 128 && dout.numel() == out.numel(), "out / dout [B, S, H * 128]");
@@ -1055,7 +1072,7 @@ std::vector<Tensor> fa_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout
   psamd::launch_fa_bwd(u16(q), u16(k), u16(v), u16(out), u16(dout), lse.data_ptr<float>(), dsum.data_ptr<float>(),
                        u16m(dq), u16m(dk), u16m(dv),
                        static_cast<int>(B), static_cast<int>(S), static_cast<int>(H), static_cast<int>(KV),
-                       1.f / std::sqrt(128.f), cur_stream(q));
+                       1.f / std::sqrt(128.f), cur_stream(q), ds, de);
   return {dq, dk, dv};
 }
 
@@ -2137,8 +2154,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_fwd", &xent_fwd, py::arg("x"), py::arg("labels"), py::arg("ignore_index"));
   m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("go"), py::arg("count"),
         py::arg("ignore_index"));
-  m.def("fa_fwd", &fa_fwd);
-  m.def("fa_bwd", &fa_bwd);
+  m.def("fa_fwd", &fa_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("doc_start") = py::none());
+  m.def("fa_bwd", &fa_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("heads"),
         py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none());
   m.def("attn_dropout_mask", &attn_dropout_mask);

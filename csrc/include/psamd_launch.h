@@ -583,10 +583,13 @@ void launch_xent_fwd(const uint16_t* x, const int64_t* lab, int64_t R, int V, in
 void launch_xent_bwd(const uint16_t* x, const int64_t* lab, const float* lse, int64_t R, int V, int64_t ignore,
                      const float* go, const float* count, uint16_t* dx, hipStream_t s);
 void launch_fa_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, float* lse, int B, int S,
-                   int H, int KV, float scale, hipStream_t s);
+                   int H, int KV, float scale, hipStream_t s, const int* doc_start = nullptr);
+// packed documents (flash_attn.hip): doc_start / doc_end (nullable, device, int32 [B, S], non-decreasing
+// along S): query i of row b sees keys doc_start[b, i] <= j <= i, key j is seen by queries
+// j <= i < doc_end[b, j]; the kernels clamp every bound into the row.  The backward takes both or neither
 void launch_fa_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
                    const float* lse, float* dsum, uint16_t* dq, uint16_t* dk, uint16_t* dv, int B, int S, int H,
-                   int KV, float scale, hipStream_t s);
+                   int KV, float scale, hipStream_t s, const int* doc_start = nullptr, const int* doc_end = nullptr);
 void launch_conv_wgrad(const ConvWgradArgs& a, hipStream_t s);
 // BN helpers for the fused bottleneck (bn_act.hip): y = act(x*scale + shift [+ res [* rscale + rshift]])
 // mbits (nullable): also write the ReLU mask of y, 1 bit per element

@@ -124,10 +124,29 @@ __device__ __forceinline__ void pv_block(const uint16_t* T, const f32x16 (&pt)[2
 // the most keys, and starting them first keeps the tail short.
 constexpr float kRescale = 8.f;
 
-template <int NW>
+// DOCS (packed documents): query i of row b sees keys doc_start[b, i] <= j <= i.  The bound is
+// non-decreasing along the row, so the block's key loop starts at the tile that holds the bound of
+// its first query, a wave skips tiles that end before the bound of its first query, and only tiles
+// that begin before the bound of its last query take the lower-bound mask (by select).  Every bound
+// is clamped to [0, query], so malformed bounds cannot move an address out of the tensors.
+__device__ __forceinline__ int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
+
+// the bounds a forward / dQ lane works with, from its row ds of doc_start: lo of its own query qi (one
+// VGPR); uniform (SGPRs): kb0, the first key tile of the block whose first query is qblk, and wlo0 /
+// wlo1, the bounds of the first and last query of the wave that begins at q0
+__device__ __forceinline__ void lower_bounds(const int* __restrict__ ds, int qi, int qblk, int q0, int& lo, int& kb0,
+                                             int& wlo0, int& wlo1) {
+  lo = clampi(ds[qi], 0, qi);
+  kb0 = clampi(ds[qblk], 0, qblk) / kBK;
+  wlo0 = __builtin_amdgcn_readfirstlane(clampi(ds[q0], 0, q0));
+  wlo1 = __builtin_amdgcn_readfirstlane(clampi(ds[q0 + 31], 0, q0 + 31));
+}
+
+template <int NW, bool DOCS>
 __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                          const uint16_t* __restrict__ v, uint16_t* __restrict__ out,
-                                                         float* __restrict__ lse, int S, int H, int KV, float scale) {
+                                                         float* __restrict__ lse, int S, int H, int KV, float scale,
+                                                         const int* __restrict__ doc_start) {
   constexpr int BQ = NW * 32, NT = NW * 64;
   constexpr int CH = kBK * 16 / NT;  // 16-B chunks per thread per tensor per tile
   static_assert(CH >= 1 && kBK * 16 % NT == 0, "tile / block shape");
@@ -144,6 +163,8 @@ __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restr
   const int q0 = qb * BQ + w * 32, qi = q0 + c;
   const int nkb = (qb * BQ + BQ - 1) / kBK + 1;
   const float k2 = scale * kLog2e;
+  int lo = 0, kb0 = 0, wlo0 = 0, wlo1 = 0;
+  if constexpr (DOCS) lower_bounds(doc_start + static_cast<int64_t>(b) * S, qi, qb * BQ, q0, lo, kb0, wlo0, wlo1);
   u16x8 kr[CH], vr[CH];
   auto gload = [&](int kb) {
 #pragma unroll
@@ -162,21 +183,22 @@ __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restr
       *reinterpret_cast<u16x8*>(Vs[buf] + off<128>(r, ch * 8)) = vr[i];
     }
   };
-  gload(0);
+  gload(kb0);
   bf16x8_t qf[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const bf16x8_t*>(qp + static_cast<int64_t>(qi) * kD + 16 * s + 8 * hl);
-  swrite(0);
-  if (nkb > 1) gload(1);
+  swrite(kb0 & 1);
+  if (kb0 + 1 < nkb) gload(kb0 + 1);
   float m2 = -INFINITY, l = 0.f;  // reference max in exp2 units (scores * scale * log2 e)
   f32x16 o[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) zero(o[db]);
-  for (int kb = 0; kb < nkb; ++kb) {
+  for (int kb = kb0; kb < nkb; ++kb) {
     __syncthreads();  // tile kb is in LDS; every wave is done with tile kb - 1's buffer
     const uint16_t* K = Ks[kb & 1];
     const uint16_t* V = Vs[kb & 1];
-    if (kb * kBK <= q0 + 31) {  // wave-uniform: skip tiles wholly in this wave's future
+    // wave-uniform: skip tiles wholly in this wave's future (DOCS: or wholly before its documents)
+    if (kb * kBK <= q0 + 31 && (!DOCS || kb * kBK + kBK - 1 >= wlo0)) {
       f32x16 st[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -193,15 +215,31 @@ __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restr
             if (key > qi) st[ks][e] = -INFINITY;
           }
       }
+      if constexpr (DOCS) {
+        if (kb * kBK < wlo1) {  // the tile begins before the last query's document: mask earlier documents
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int key = kb * kBK + ks * 32 + (e & 3) + 8 * (e >> 2) + 4 * hl;
+              if (key < lo) st[ks][e] = -INFINITY;
+            }
+        }
+      }
       float mb = st[0][0];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int e = 0; e < 16; ++e) mb = fmaxf(mb, st[ks][e]);
-      mb = xhalf_max(mb) * k2;  // every processed tile holds >= 1 visible key per query
-      if (!__all(mb - m2 <= kRescale)) {
+      // plain: every processed tile holds >= 1 visible key per query.  DOCS: a lane whose document
+      // begins after the tile sees none of it (mb = -inf, maybe m2 = -inf too) and passes through
+      // unchanged: no vote for a rescale, alpha = 1, p = 0 -- by select, the other lanes compute
+      // what they always did
+      mb = xhalf_max(mb) * k2;
+      const bool vis = !DOCS || mb > -INFINITY;
+      if (!__all(!vis || mb - m2 <= kRescale)) {
         const float mn = fmaxf(m2, mb);
-        const float alpha = fast_exp2(m2 - mn);
+        const float alpha = vis ? fast_exp2(m2 - mn) : 1.f;
         l *= alpha;
 #pragma unroll
         for (int db = 0; db < 4; ++db)
@@ -209,12 +247,13 @@ __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restr
           for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
         m2 = mn;
       }
+      const float mr = vis ? m2 : 0.f;  // exp2(-inf - 0) = 0 where m2 is still -inf
       float ls = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const float p = fast_exp2(st[ks][e] * k2 - m2);
+          const float p = fast_exp2(st[ks][e] * k2 - mr);
           st[ks][e] = p;
           ls += p;
         }
@@ -239,7 +278,8 @@ __global__ __launch_bounds__(NW * 64) void fa_fwd_kernel(const uint16_t* __restr
 // The forward's structure (NW waves x 32 queries sharing double-buffered K / V tiles prefetched
 // two tiles ahead, one barrier per tile), with each 64-key tile taken as two 32-key halves so S^T,
 // dP^T and dS^T of only one half are live: at 8 waves the kernel fits two waves per SIMD.
-template <int NW>
+// DOCS: the forward's tile range and skips; masked P is set to 0 by select.
+template <int NW, bool DOCS>
 __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __restrict__ q,
                                                             const uint16_t* __restrict__ k,
                                                             const uint16_t* __restrict__ v,
@@ -247,7 +287,7 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
                                                             const uint16_t* __restrict__ dout,
                                                             const float* __restrict__ lse, float* __restrict__ dsum,
                                                             uint16_t* __restrict__ dq, int S, int H, int KV,
-                                                            float scale) {
+                                                            float scale, const int* __restrict__ doc_start) {
   constexpr int BQ = NW * 32, NT = NW * 64;
   constexpr int CH = kBK * 16 / NT;
   static_assert(CH >= 1 && kBK * 16 % NT == 0, "tile / block shape");
@@ -263,6 +303,8 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
   const uint16_t* vp = v + static_cast<int64_t>(b * KV + kvh) * S * kD;
   const int q0 = qb * BQ + w * 32, qi = q0 + c;
   const int nkb = (qb * BQ + BQ - 1) / kBK + 1;
+  int lo = 0, kb0 = 0, wlo0 = 0, wlo1 = 0;
+  if constexpr (DOCS) lower_bounds(doc_start + static_cast<int64_t>(b) * S, qi, qb * BQ, q0, lo, kb0, wlo0, wlo1);
   u16x8 kr[CH], vr[CH];
   auto gload = [&](int kb) {
 #pragma unroll
@@ -281,7 +323,7 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
       *reinterpret_cast<u16x8*>(Vs[buf] + off<128>(r, ch * 8)) = vr[i];
     }
   };
-  gload(0);
+  gload(kb0);
   const int64_t orow = (static_cast<int64_t>(b) * S + qi) * H * kD + h * kD;
   bf16x8_t qf[8], df[8];
   float dd = 0.f;
@@ -298,20 +340,23 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
   const int64_t li = static_cast<int64_t>(b * H + h) * S + qi;
   if (hl == 0) dsum[li] = dd;
   const float l2 = lse[li] * kLog2e, k2 = scale * kLog2e;
-  swrite(0);
-  if (nkb > 1) gload(1);
+  swrite(kb0 & 1);
+  if (kb0 + 1 < nkb) gload(kb0 + 1);
   f32x16 acc[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) zero(acc[db]);
-  for (int kb = 0; kb < nkb; ++kb) {
+  for (int kb = kb0; kb < nkb; ++kb) {
     __syncthreads();
     const uint16_t* K = Ks[kb & 1];
     const uint16_t* V = Vs[kb & 1];
-    if (kb * kBK <= q0 + 31) {
+    if (kb * kBK <= q0 + 31 && (!DOCS || kb * kBK + kBK - 1 >= wlo0)) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const int kk0 = kb * kBK + ks * 32;
         if (kk0 > q0 + 31) continue;  // wave-uniform: this half is wholly in the future
+        if constexpr (DOCS) {
+          if (kk0 + 31 < wlo0) continue;  // wave-uniform: wholly before this wave's documents
+        }
         f32x16 st, dp;
         zero(st);
         zero(dp);
@@ -320,7 +365,15 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
           st = mma(frag<128>(K, ks * 32 + c, 2 * s + hl), qf[s], st);
           dp = mma(frag<128>(V, ks * 32 + c, 2 * s + hl), df[s], dp);  // dP^T = V dO^T
         }
-        if (kk0 + 31 > q0) {  // wave-uniform: only the diagonal half-tile needs the causal mask
+        if (DOCS && kk0 < wlo1) {  // wave-uniform: the half begins before the last query's document
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            float p = fast_exp2(st[e] * k2 - l2);
+            const int key = kk0 + (e & 3) + 8 * (e >> 2) + 4 * hl;
+            if (key > qi || key < lo) p = 0.f;
+            st[e] = p * (dp[e] - dd);
+          }
+        } else if (kk0 + 31 > q0) {  // wave-uniform: only the diagonal half-tile needs the causal mask
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             float p = fast_exp2(st[e] * k2 - l2);
@@ -369,13 +422,20 @@ __device__ __forceinline__ f32x4 lds_f4(const float* p) {
 }
 __device__ __forceinline__ void tie4(f32x4& v) { asm volatile("" : "+v"(v)); }
 
+//
+// DOCS: key j is seen by queries j <= i < doc_end[b, j] (non-decreasing along the row).  The block's
+// query stages end with the document of its last key, a wave skips the 32-query slices at or beyond
+// the bound of its last key, and slices that reach the bound of its first key take the upper-bound
+// mask (by select).  Every bound is clamped to [key + 1, S].
+template <bool DOCS>
 __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __restrict__ q,
                                                           const uint16_t* __restrict__ k,
                                                           const uint16_t* __restrict__ v,
                                                           const uint16_t* __restrict__ dout,
                                                           const float* __restrict__ lse,
                                                           const float* __restrict__ dsum, uint16_t* __restrict__ dko,
-                                                          uint16_t* __restrict__ dvo, int S, int H, int KV, float scale) {
+                                                          uint16_t* __restrict__ dvo, int S, int H, int KV, float scale,
+                                                          const int* __restrict__ doc_end) {
   __shared__ __attribute__((aligned(16))) uint16_t Qs[2][kBQS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t dOs[2][kBQS * kD];
   __shared__ __attribute__((aligned(16))) float Ls[2][kBQS];
@@ -389,7 +449,16 @@ __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __rest
   const uint16_t* vp = v + static_cast<int64_t>(b * KV + kvh) * S * kD;
   const int k0 = kblk * kBQ + w * 32, key = k0 + c;
   // stages: (q head g, query stage qs) for qs from this key block's first query on
-  const int qs0 = kblk * kBQ / kBQS, nqs = S / kBQS, per = nqs - qs0, nst = G * per;
+  // (DOCS: up to the stage that holds the end of the block's last key's document)
+  int hi = S, nqs = S / kBQS, whi0 = S, whi1 = S;
+  if constexpr (DOCS) {
+    const int* de = doc_end + static_cast<int64_t>(b) * S;
+    hi = clampi(de[key], key + 1, S);
+    nqs = (clampi(de[kblk * kBQ + kBQ - 1], kblk * kBQ + kBQ, S) + kBQS - 1) / kBQS;
+    whi0 = __builtin_amdgcn_readfirstlane(clampi(de[k0], k0 + 1, S));
+    whi1 = __builtin_amdgcn_readfirstlane(clampi(de[k0 + 31], k0 + 32, S));
+  }
+  const int qs0 = kblk * kBQ / kBQS, per = nqs - qs0, nst = G * per;
   auto issue = [&](int st) {
     const int g = st / per, qs = qs0 + st % per, h = kvh * G + g, buf = st & 1;
     const int64_t li = static_cast<int64_t>(b * H + h) * S + qs * kBQS;
@@ -424,6 +493,9 @@ __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __rest
     for (int sl = 0; sl < kBQS / 32; ++sl) {
       const int qr0 = qbase + sl * 32;
       if (qr0 + 31 < k0) continue;  // wave-uniform: every query precedes every key of this wave
+      if constexpr (DOCS) {
+        if (qr0 >= whi1) continue;  // wave-uniform: every query is beyond this wave's documents
+      }
       f32x4 lv[4], dv4[4];
       bf16x8_t qa[8], da[8];
 #pragma unroll
@@ -461,7 +533,16 @@ __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __rest
           ta[s2][db] = tfrag_a<128>(dO, sl * 2 + s2, db * 32, lane);
           tq[s2][db] = tfrag_a<128>(Q, sl * 2 + s2, db * 32, lane);
         }
-      if (k0 + 31 > qr0) {  // wave-uniform: only slices on the diagonal need the causal mask
+      if (DOCS && qr0 + 31 >= whi0) {  // wave-uniform: the slice reaches the end of the first key's document
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float p = fast_exp2(sa[e] * k2 - lv[e >> 2][e & 3] * kLog2e);
+          const int qr = qr0 + (e & 3) + 8 * (e >> 2) + 4 * hl;
+          if (key > qr || qr >= hi) p = 0.f;
+          sa[e] = p;
+          dp[e] = p * (dp[e] - dv4[e >> 2][e & 3]);
+        }
+      } else if (k0 + 31 > qr0) {  // wave-uniform: only slices on the diagonal need the causal mask
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           float p = fast_exp2(sa[e] * k2 - lv[e >> 2][e & 3] * kLog2e);
@@ -514,25 +595,27 @@ __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __rest
 
 }  // namespace
 
+// doc_start / doc_end (device int32 [B, S], or nullptr): the document instantiations; nullptr selects
+// the plain ones, which compile to what they were without the DOCS parameter
 void launch_fa_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, float* lse, int B, int S,
-                   int H, int KV, float scale, hipStream_t s) {
-  if (S % 256 == 0)
-    hipLaunchKernelGGL(fa_fwd_kernel<8>, dim3(S / 256 * H * B), dim3(512), 0, s, q, k, v, out, lse, S, H, KV, scale);
-  else
-    hipLaunchKernelGGL(fa_fwd_kernel<4>, dim3(S / kBQ * H * B), dim3(256), 0, s, q, k, v, out, lse, S, H, KV, scale);
+                   int H, int KV, float scale, hipStream_t s, const int* doc_start) {
+  const bool w8 = S % 256 == 0;
+  auto* kern = w8 ? (doc_start ? fa_fwd_kernel<8, true> : fa_fwd_kernel<8, false>)
+                  : (doc_start ? fa_fwd_kernel<4, true> : fa_fwd_kernel<4, false>);
+  hipLaunchKernelGGL(kern, dim3(S / (w8 ? 256 : kBQ) * H * B), dim3(w8 ? 512 : 256), 0, s, q, k, v, out, lse, S, H, KV,
+                     scale, doc_start);
 }
 
 void launch_fa_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
                    const float* lse, float* dsum, uint16_t* dq, uint16_t* dk, uint16_t* dv, int B, int S, int H,
-                   int KV, float scale, hipStream_t s) {
-  if (S % 256 == 0)
-    hipLaunchKernelGGL(fa_bwd_dq_kernel<8>, dim3(S / 256 * H * B), dim3(512), 0, s, q, k, v, out, dout, lse, dsum, dq, S,
-                       H, KV, scale);
-  else
-    hipLaunchKernelGGL(fa_bwd_dq_kernel<4>, dim3(S / kBQ * H * B), dim3(256), 0, s, q, k, v, out, dout, lse, dsum, dq, S,
-                       H, KV, scale);
-  hipLaunchKernelGGL(fa_bwd_dkdv_kernel, dim3(S / kBQ * KV * B), dim3(256), 0, s, q, k, v, dout, lse, dsum, dk, dv, S,
-                     H, KV, scale);
+                   int KV, float scale, hipStream_t s, const int* doc_start, const int* doc_end) {
+  const bool w8 = S % 256 == 0, docs = doc_start != nullptr;
+  auto* kq = w8 ? (docs ? fa_bwd_dq_kernel<8, true> : fa_bwd_dq_kernel<8, false>)
+                : (docs ? fa_bwd_dq_kernel<4, true> : fa_bwd_dq_kernel<4, false>);
+  hipLaunchKernelGGL(kq, dim3(S / (w8 ? 256 : kBQ) * H * B), dim3(w8 ? 512 : 256), 0, s, q, k, v, out, dout, lse, dsum,
+                     dq, S, H, KV, scale, doc_start);
+  hipLaunchKernelGGL(docs ? fa_bwd_dkdv_kernel<true> : fa_bwd_dkdv_kernel<false>, dim3(S / kBQ * KV * B), dim3(256), 0,
+                     s, q, k, v, dout, lse, dsum, dk, dv, S, H, KV, scale, doc_end);
 }
 
 }  // namespace psamd

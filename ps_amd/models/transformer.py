@@ -6,7 +6,8 @@ and counts match the published architectures -- BERT-base 110M (12 x 768, 12 hea
 3072, vocab 30522), Llama-3-8B 8.03B (32 x 4096, 32 q / 8 kv heads, FFN 14336, vocab
 128256, RoPE theta 500000).  BERT attention (S <= 128) runs the fused MFMA kernel of
 csrc/kernels/attention.hip (right-padded batches too: ``BertForMLM.forward(..., lengths=)``,
-``mlm_batch(..., lengths=)``), Llama's causal GQA attention the flash kernel of flash_attn.hip;
+``mlm_batch(..., lengths=)``), Llama's causal GQA attention the flash kernel of flash_attn.hip
+(packed rows too: ``LlamaForCausalLM.forward(..., doc_ids=)``, ``packed_lm_batch``);
 everything is bf16 on the GPU with fp32 masters on the parameter-server shards.
 """
 from __future__ import annotations
@@ -22,8 +23,8 @@ from torch.utils.checkpoint import checkpoint
 
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
-from ..ops.transformer import (attention_causal_gqa, attention_qkv, cross_entropy, layer_norm_residual, rms_norm, rope_split,
-                              rope_table, swiglu)
+from ..ops.transformer import (attention_causal_gqa, attention_qkv, cross_entropy, doc_bounds as _doc_bounds,
+                              layer_norm_residual, rms_norm, rope_split, rope_table, swiglu)
 
 
 # ------------------------------------------------------------------------------------ BERT
@@ -225,10 +226,11 @@ class LlamaBlock(nn.Module):
         self.w13 = PsLinear(c.hidden, 2 * c.ffn, bias=False)
         self.w2 = PsLinear(c.ffn, c.hidden, bias=False)
 
-    def forward(self, x, r, cs):
+    def forward(self, x, r, cs, doc_bounds=None):
         """Residual stream = x + r (r: the previous block's pending MLP output, None for the
         first block) -- the add is fused into this block's first RMSNorm, and this block's
-        MLP output is returned pending for the next one."""
+        MLP output is returned pending for the next one.  ``doc_bounds`` (packed rows): the
+        (doc_start, doc_end) pair of ops.transformer.doc_bounds, each token attends inside its document."""
         b, s, _ = x.shape
         c = self.c
         hd = c.hidden // c.heads
@@ -238,7 +240,7 @@ class LlamaBlock(nn.Module):
             x, h = rms_norm(x, self.attn_norm.weight, c.eps, residual=r)
         qkv = self.wqkv(h).view(b, s, c.heads + 2 * c.kv_heads, hd)
         q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads)  # RoPE + split + transpose, one pass
-        o = self.wo(attention_causal_gqa(q, k, v))  # flash kernel (heads merged) or SDPA
+        o = self.wo(attention_causal_gqa(q, k, v, doc_bounds))  # flash kernel (heads merged) or SDPA
         x, h = rms_norm(x, self.mlp_norm.weight, c.eps, residual=o)
         return x, self.w2(swiglu(self.w13(h)))
 
@@ -256,22 +258,56 @@ class LlamaForCausalLM(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, ids, labels=None):
+    def forward(self, ids, labels=None, doc_ids=None):
+        """``doc_ids`` [B, S] (any integer dtype): packed rows -- a new document begins wherever the id
+        changes along a row, and a token attends only to earlier tokens of its own document (the bounds
+        are computed once and given to every layer).  RoPE positions run on through the row: the
+        scores depend on i - j alone, so inside a document they are those of restarted positions.  A
+        position whose next token belongs to another document has no target."""
         s = ids.shape[1]
         cs = rope_table(s, self.c.hidden // self.c.heads, self.c.rope_theta, ids.device)
+        bounds = None
+        if doc_ids is not None:
+            doc_ids = doc_ids.to(ids.device, non_blocking=True)
+            if doc_ids.shape != ids.shape:
+                raise ValueError("doc_ids: [B, S] like ids")
+            bounds = _doc_bounds(doc_ids)
         x, r = self.embed(ids), None
         for layer in self.layers:
             if self.checkpointing and self.training:
-                x, r = checkpoint(layer, x, r, cs, use_reentrant=False)
+                x, r = checkpoint(layer, x, r, cs, bounds, use_reentrant=False)
             else:
-                x, r = layer(x, r, cs)
+                x, r = layer(x, r, cs, bounds)
         _, h = rms_norm(x, self.norm.weight, self.c.eps, residual=r)
         logits = self.lm_head(h)
         if labels is None:
             return logits
         # next-token targets; the last position has none (ignored) -- no sliced copy of the logits
         tgt = torch.cat([labels[:, 1:], torch.full_like(labels[:, :1], -100)], dim=1)
+        if doc_ids is not None:  # nor has a document's last position
+            tgt[:, :-1].masked_fill_(doc_ids[:, 1:] != doc_ids[:, :-1], -100)
         return cross_entropy(logits, tgt, ignore_index=-100)
+
+
+def packed_lm_batch(batch: int, seq: int, vocab: int, doc_lengths, seed: int = 0, device=None):
+    """Synthetic packed causal-LM batch -> (ids, labels, doc_ids), each [batch, seq] int64:
+    ``doc_lengths`` is one list of document lengths per row, each list summing to ``seq``
+    (``ValueError`` otherwise); ``doc_ids`` numbers a row's documents 0, 1, ... and ``labels`` are the
+    ids (``LlamaForCausalLM.forward(ids, labels, doc_ids)`` shifts them and drops the targets that
+    would cross a document boundary)."""
+    rows = [list(map(int, r)) for r in doc_lengths]
+    if len(rows) != batch:
+        raise ValueError("packed_lm_batch: one list of document lengths per row")
+    for r in rows:
+        if not r or min(r) < 1 or sum(r) != seq:
+            raise ValueError("packed_lm_batch: every row's positive document lengths sum to seq")
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(0, vocab, (batch, seq), generator=g)
+    doc_ids = torch.stack([torch.repeat_interleave(torch.arange(len(r)), torch.tensor(r)) for r in rows])
+    labels = ids.clone()
+    if device is not None:
+        ids, labels, doc_ids = ids.to(device), labels.to(device), doc_ids.to(device)
+    return ids, labels, doc_ids
 
 
 def param_count(m: nn.Module) -> int:

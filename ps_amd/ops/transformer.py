@@ -7,8 +7,9 @@
   attention_qkv(qkv, H, p, mask, key_lengths) -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
                                                  projection (csrc/kernels/attention.hip, S <= 128;
                                                  right-padded batches by per-sequence key_lengths)
-  attention_causal_gqa(q, k, v)               -> causal GQA flash attention, heads merged
-                                                 (csrc/kernels/flash_attn.hip, head dim 128)
+  attention_causal_gqa(q, k, v, doc_bounds)   -> causal GQA flash attention, heads merged
+                                                 (csrc/kernels/flash_attn.hip, head dim 128; packed
+                                                 rows by per-token document bounds: doc_bounds(doc_ids))
 
 GPU bf16 tensors (row length <= 4096, multiple of 8) take the HIP kernels; everything else
 runs the plain torch composition, which is also the numerics oracle in the GPU tests.
@@ -261,27 +262,83 @@ def flash_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
             and q.shape[1] % k.shape[1] == 0 and knobs.enabled("flash_attn"))
 
 
+def doc_bounds(doc_ids: torch.Tensor):
+    """Per-token document bounds of packed rows: ``doc_ids`` [B, S] (any integer dtype) ->
+    (``doc_start``, ``doc_end``), int32 [B, S] on its device, computed there without a sync.  A new
+    document begins at position 0 and wherever ``doc_ids[b, i] != doc_ids[b, i - 1]`` (the values mean
+    nothing else; a pad tail is one more document).  ``doc_start[b, i]`` is the first position of
+    the document that holds i, ``doc_end[b, i]`` one past its last: start <= i < end, both
+    non-decreasing along the row."""
+    if doc_ids.dim() != 2:
+        raise ValueError("doc_bounds: doc_ids [B, S]")
+    if doc_ids.is_floating_point() or doc_ids.is_complex() or doc_ids.dtype == torch.bool:
+        raise ValueError("doc_bounds: an integer tensor")
+    b, s = doc_ids.shape
+    pos = torch.arange(s, device=doc_ids.device, dtype=torch.int32).expand(b, s)
+    edge = doc_ids[:, 1:] != doc_ids[:, :-1]
+    one = torch.ones(b, 1, dtype=torch.bool, device=doc_ids.device)
+    new = torch.cat([one, edge], dim=1)   # a document begins here
+    last = torch.cat([edge, one], dim=1)  # a document ends here
+    start = torch.where(new, pos, torch.zeros_like(pos)).cummax(1).values
+    end = torch.where(last, pos + 1, torch.full_like(pos, s)).flip(1).cummin(1).values.flip(1)
+    return start.contiguous(), end.contiguous()
+
+
+def _check_doc_bounds(bounds, q: torch.Tensor):
+    """(doc_start, doc_end) as int32 [B, S] tensors on q's device, no sync."""
+    try:
+        start, end = bounds
+    except (TypeError, ValueError):
+        raise ValueError("attention_causal_gqa: doc_bounds is (doc_start, doc_end)") from None
+    want = (q.shape[0], q.shape[2])
+    for t in (start, end):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+            raise ValueError("attention_causal_gqa: doc_start / doc_end [B, S]")
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("attention_causal_gqa: doc_start / doc_end integer tensors")
+    return tuple(t.to(device=q.device, dtype=torch.int32, non_blocking=True).contiguous() for t in (start, end))
+
+
 class _FlashCausal(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v):
+    def forward(ctx, q, k, v, doc_start=None, doc_end=None):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = native().fa_fwd(q, k, v)
-        ctx.save_for_backward(q, k, v, out, lse)
+        if doc_start is None:
+            out, lse = native().fa_fwd(q, k, v)
+            ctx.save_for_backward(q, k, v, out, lse)
+        else:
+            out, lse = native().fa_fwd(q, k, v, doc_start)
+            ctx.save_for_backward(q, k, v, out, lse, doc_start, doc_end)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
-        return tuple(native().fa_bwd(q, k, v, out, dout.contiguous(), lse))
+        q, k, v, out, lse, *bounds = ctx.saved_tensors
+        return tuple(native().fa_bwd(q, k, v, out, dout.contiguous(), lse, *bounds)) + (None, None)
 
 
-def attention_causal_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+def attention_causal_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, doc_bounds=None) -> torch.Tensor:
     """Causal attention with grouped KV heads: q [B, H, S, D], k / v [B, KV, S, D] -> [B, S, H * D]
-    (heads merged, the output projection's input layout)."""
+    (heads merged, the output projection's input layout).
+
+    ``doc_bounds`` = (doc_start, doc_end) (``doc_bounds(doc_ids)``; integer [B, S]) describes packed
+    rows: query i of row b sees keys ``doc_start[b, i] <= j <= i`` only, its own document.  In the
+    flash domain this stays on the in-house kernels, which also skip the key tiles no query of a block
+    can see; off it (CPU, fp32, head dim other than 128, S % 128 != 0, PS_AMD_DISABLE=flash_attn) SDPA
+    gets the dense boolean mask [B, 1, S, S] built from doc_start."""
+    if doc_bounds is None:
+        if flash_ok(q, k, v):
+            return _FlashCausal.apply(q, k, v)
+        b, _, s, _ = q.shape
+        a = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=True)
+        return a.transpose(1, 2).reshape(b, s, -1)
+    start, end = _check_doc_bounds(doc_bounds, q)
     if flash_ok(q, k, v):
-        return _FlashCausal.apply(q, k, v)
+        return _FlashCausal.apply(q, k, v, start, end)
     b, _, s, _ = q.shape
-    a = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=True)
+    pos = torch.arange(s, device=q.device)
+    mask = (pos[None, None, :] <= pos[None, :, None]) & (pos[None, None, :] >= start[:, :, None])  # [B, S(q), S(k)]
+    a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask[:, None], enable_gqa=True)
     return a.transpose(1, 2).reshape(b, s, -1)
 
 
