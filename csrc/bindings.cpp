@@ -942,9 +942,43 @@ static const int32_t* attn_klen(const c10::optional<Tensor>& key_lengths, const 
   return k.data_ptr<int32_t>();
 }
 
-std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths) {
-  check_attn(qkv, heads);
+// cu_seqlens (optional, int32 [B + 1] on qkv's device) with max_len: a packed batch, qkv [T, 3 * heads * 64]
+// -> [out [T, heads * 64], lse [heads, T]].  Only the layout is checked: the kernels clamp every sequence
+// into the T rows (looking at the values would be a host sync).  Returns nullptr without cu_seqlens.
+static const int32_t* attn_cu(const c10::optional<Tensor>& cu_seqlens, int64_t max_len,
+                              const c10::optional<Tensor>& key_lengths, const Tensor& qkv, int64_t heads) {
+  if (!cu_seqlens.has_value()) {
+    TORCH_CHECK(max_len == 0, "max_len goes with cu_seqlens");
+    return nullptr;
+  }
+  TORCH_CHECK(!key_lengths.has_value(), "give key_lengths or cu_seqlens, not both");
+  const Tensor& cu = *cu_seqlens;
+  check_rows(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 2 && heads > 0 && qkv.size(1) == 3 * heads * 64 && qkv.size(0) > 0,
+              "packed qkv [T, 3 * heads * 64]");
+  TORCH_CHECK(qkv.size(0) < (int64_t(1) << 31), "T");
+  TORCH_CHECK(cu.device() == qkv.device(), "cu_seqlens on qkv's device");
+  TORCH_CHECK(cu.scalar_type() == torch::kInt32 && cu.is_contiguous() && cu.dim() == 1 && cu.numel() >= 2,
+              "cu_seqlens int32, contiguous, [B + 1] with B >= 1");
+  TORCH_CHECK(max_len > 0 && max_len % 32 == 0 && max_len <= 128, "max_len a multiple of 32, <= 128");
+  TORCH_CHECK((cu.numel() - 1) * heads < (int64_t(1) << 31), "batch * heads");
+  return cu.data_ptr<int32_t>();
+}
+
+std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths,
+                             c10::optional<Tensor> cu_seqlens, int64_t max_len) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p in [0, 1)");
+  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads)) {
+    const int64_t T = qkv.size(0), B = cu_seqlens->numel() - 1;
+    const c10::DeviceGuard guard(qkv.device());
+    auto out = torch::empty({T, heads * 64}, qkv.options());
+    auto lse = torch::empty({heads, T}, qkv.options().dtype(torch::kFloat32));
+    psamd::launch_attn_fwd(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(max_len),
+                           static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed),
+                           cur_stream(qkv), nullptr, cu, static_cast<int>(T));
+    return {out, lse};
+  }
+  check_attn(qkv, heads);
   const int64_t B = qkv.size(0), S = qkv.size(1);
   const int32_t* klen = attn_klen(key_lengths, qkv);
   const c10::DeviceGuard guard(qkv.device());
@@ -957,7 +991,24 @@ std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, 
 }
 
 Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed,
-                c10::optional<Tensor> key_lengths) {
+                c10::optional<Tensor> key_lengths, c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads)) {
+    const int64_t T = qkv.size(0), B = cu_seqlens->numel() - 1;
+    check_rows(out, "out");
+    check_rows(dout, "dout");
+    TORCH_CHECK(out.sizes() == torch::IntArrayRef({T, heads * 64}) && dout.sizes() == out.sizes(),
+                "packed out / dout [T, heads * 64]");
+    check_gpu(lse, "lse");
+    TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                    lse.sizes() == torch::IntArrayRef({heads, T}),
+                "packed lse fp32 [heads, T]");
+    const c10::DeviceGuard guard(qkv.device());
+    auto dqkv = torch::empty_like(qkv);
+    psamd::launch_attn_bwd(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B),
+                           static_cast<int>(max_len), static_cast<int>(heads), 0.125f, static_cast<float>(p),
+                           static_cast<uint64_t>(seed), cur_stream(qkv), nullptr, cu, static_cast<int>(T));
+    return dqkv;
+  }
   check_attn(qkv, heads);
   const int64_t B = qkv.size(0), S = qkv.size(1);
   const int32_t* klen = attn_klen(key_lengths, qkv);
@@ -2150,7 +2201,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
-        py::arg("key_lengths") = py::none());
+        py::arg("key_lengths") = py::none(), py::arg("cu_seqlens") = py::none(), py::arg("max_len") = 0);
   m.def("xent_fwd", &xent_fwd, py::arg("x"), py::arg("labels"), py::arg("ignore_index"));
   m.def("xent_bwd", &xent_bwd, py::arg("x"), py::arg("labels"), py::arg("lse"), py::arg("go"), py::arg("count"),
         py::arg("ignore_index"));
@@ -2158,7 +2209,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_bwd", &fa_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"),
         py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("heads"),
-        py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none());
+        py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none(), py::arg("cu_seqlens") = py::none(),
+        py::arg("max_len") = 0);
   m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -567,12 +567,17 @@ int64_t conv_wgrad_ws(int M, int N, int K, int C, bool pro);
 // Fused short-sequence attention (attention.hip): qkv [B, S, 3, H, 64] bf16 (Linear layout),
 // out [B, S, H * 64], lse [B, H, S] fp32; S % 32 == 0, S <= 128; dropout p on the probabilities.
 // klen (nullable, device, [B]): right-padded batch -- keys >= clamp(klen[b], 1, S) of sequence b take
-// no part in the softmax (a key-padding mask), dk / dv rows there are zeros; nullptr: no padding
+// no part in the softmax (a key-padding mask), dk / dv rows there are zeros; nullptr: no padding.
+// cu (nullable, device, [B + 1], not together with klen): packed batch -- the tensors hold the T valid
+// tokens only, qkv [T, 3, H, 64], out [T, H * 64], lse [H, T]; sequence b is rows [cu[b], cu[b + 1]), and
+// S is the bound the kernels run with (>= every length, S % 32 == 0, S <= 128; the S of the dropout
+// indices).  The kernels clamp what cu says into the T rows.
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int S, int H, float scale, float p,
-                     uint64_t seed, hipStream_t s, const int32_t* klen = nullptr);
+                     uint64_t seed, hipStream_t s, const int32_t* klen = nullptr, const int32_t* cu = nullptr,
+                     int T = 0);
 void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, uint16_t* dqkv,
                      int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s,
-                     const int32_t* klen = nullptr);
+                     const int32_t* klen = nullptr, const int32_t* cu = nullptr, int T = 0);
 void launch_attn_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, hipStream_t s);
 // Causal GQA flash attention (flash_attn.hip): q [B, H, S, 128], k / v [B, KV, S, 128] bf16,
 // out [B, S, H * 128], lse / dsum [B, H, S] fp32; S % 128 == 0

@@ -144,6 +144,25 @@ __device__ __forceinline__ void stage64n(uint16_t* const (&T)[N], const uint16_t
 // block the pad keys are excluded by SELECT (a pad row may hold any finite value, one whose score
 // overflows exp2 included).  LEN = false is the unpadded kernel, unchanged.
 //
+//
+// Packed batches (PACK, implies LEN): the tensors hold the valid tokens only, qkv [T, 3, H, 64], out
+// [T, H * 64], lse [H, T]; cu [B + 1] is the exclusive prefix sum of the lengths.  Sequence b's rows
+// start at cu[b], L = cu[b + 1] - cu[b] is its key AND its query bound, S is only the bound the kernel
+// runs with (max length rounded up to 32) and the S of the dropout element indices -- a packed call
+// draws the masks of the key-length call at that S.  Nothing is read or written at or beyond row L (the
+// next sequence's token, or the end of the allocation): loads clamp to row L - 1, stores are guarded.
+// L is clamped into [0, min(S, T)] and the base into [0, T - L], so no cu can leave the tensors.
+struct PackRows {
+  int64_t row0;
+  int L;
+};
+__device__ __forceinline__ PackRows pack_rows(const int32_t* __restrict__ cu, int b, int S, int T) {
+  const int c0 = cu[b], c1 = cu[b + 1];
+  const int64_t d = static_cast<int64_t>(c1) - c0;
+  const int L = static_cast<int>(min(max(d, int64_t{0}), static_cast<int64_t>(min(S, T))));
+  return {static_cast<int64_t>(min(max(c0, 0), T - L)), L};
+}
+
 // is accumulator element e of key block kb, on lane half hl, a key below L
 __device__ __forceinline__ bool key_ok(int kb, int e, int hl, int L) {
   return kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hl < L;
@@ -151,23 +170,31 @@ __device__ __forceinline__ bool key_ok(int kb, int e, int hl, int L) {
 
 // ------------------------------------------------------------------------------ forward
 // (LEN asks for 3 blocks per CU: without the hint the allocator ends 2 VGPRs above that step)
-template <bool DROP, bool LEN>
+template <bool DROP, bool LEN, bool PACK>
 __global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse, int S, int H, float scale,
-    uint64_t seed, uint32_t thr, float rkeep, const int32_t* __restrict__ klen) {
+    uint64_t seed, uint32_t thr, float rkeep, const int32_t* __restrict__ klen, int T) {
+  static_assert(LEN || !PACK, "PACK implies LEN");
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[kS * kD];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, hl = lane >> 5, c = lane & 31;
-  int L = S;  // key bound
-  if constexpr (LEN) L = min(max(klen[b], 1), S);
+  int L = S;  // key bound (PACK: the query bound too)
+  if constexpr (LEN && !PACK) L = min(max(klen[b], 1), S);
   const int64_t rs = 3LL * H * kD;
   const uint16_t* base = qkv + static_cast<int64_t>(b) * S * rs + h * kD;
+  int64_t row0 = 0;  // PACK: the sequence's first row
+  if constexpr (PACK) {
+    const PackRows pr = pack_rows(klen, b, S, T);
+    L = pr.L, row0 = pr.row0;
+    if (L == 0) return;  // block-uniform, before any barrier
+    base = qkv + row0 * rs + h * kD;
+  }
   const int q0 = w * 32;
   // Q^T as the B operand: lane holds Q[q0 + c][16 s + 8 hl + e] -- loaded before the K / V staging
   // so its latency overlaps theirs
   bf16x8_t qf[4];
-  const int qr = min(q0 + c, S - 1);
+  const int qr = min(q0 + c, (PACK ? L : S) - 1);
 #pragma unroll
   for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8_t*>(base + qr * rs + 16 * s + 8 * hl);
   {
@@ -178,7 +205,7 @@ __global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
     stage64n<2>(tt, ss, rr, nr);
   }
   __syncthreads();
-  if (q0 >= S) return;  // no barrier below
+  if (q0 >= (PACK ? L : S)) return;  // no barrier below
   const int nkb = LEN ? (L + 31) >> 5 : S >> 5;
   f32x16 st[4];
 #pragma unroll
@@ -223,7 +250,11 @@ __global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
   }
   const float inv = 1.f / sum;
   const int q = q0 + c;
-  if (hl == 0) lse[static_cast<int64_t>(bh) * S + q] = m * scale + __logf(sum);
+  if constexpr (PACK) {  // lanes at or beyond L computed on row L - 1: they store nothing
+    if (hl == 0 && q < L) lse[static_cast<int64_t>(h) * T + row0 + q] = m * scale + __logf(sum);
+  } else {
+    if (hl == 0) lse[static_cast<int64_t>(bh) * S + q] = m * scale + __logf(sum);
+  }
   const uint32_t rowbase = (static_cast<uint32_t>(bh) * S + q) * S;
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb)
@@ -258,6 +289,10 @@ __global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
   }
   // lane column q, rows d = db*32 + (e & 3) + 8 (e >> 2) + 4 hl: 4 consecutive d per 8-B store
   uint16_t* orow = out + (static_cast<int64_t>(b) * S + q) * H * kD + h * kD;
+  if constexpr (PACK) {
+    if (q >= L) return;
+    orow = out + (row0 + q) * H * kD + h * kD;
+  }
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -273,12 +308,17 @@ __global__ __launch_bounds__(256, LEN ? 3 : 1) void attn_fwd_kernel(
 // keys >= L are zeros by select -- the V fragments come straight from global memory, pad rows
 // included -- so dK / dV rows [L, S) are exact zeros: a key wave at or beyond L stores them without
 // running its GEMMs, the pad keys inside the partly valid block get them from the zero columns of T.
-template <bool DROP, bool LEN>
+// PACK: L bounds the queries as well.  Q, K and dO are staged with L; the O / dO / lse rows and the V
+// fragments are read at min(row, L - 1); rows >= L of T are written as zeros (one select per lane, where
+// idle waves' rows are zeroed), so a lane on a clamped row adds nothing to dK / dV, and the 16-query
+// steps at or beyond L, which would add exact zeros, are not run; only rows < L of dqkv are stored.
+template <bool DROP, bool LEN, bool PACK>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                        const uint16_t* __restrict__ dout, const float* __restrict__ lse,
                                                        uint16_t* __restrict__ dqkv, int S, int H, float scale,
                                                        uint64_t seed, uint32_t thr, float rkeep,
-                                                       const int32_t* __restrict__ klen) {
+                                                       const int32_t* __restrict__ klen, int T_) {
+  static_assert(LEN || !PACK, "PACK implies LEN");
   __shared__ __attribute__((aligned(16))) uint16_t Qs[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t Ks[kS * kD];
   __shared__ __attribute__((aligned(16))) uint16_t dOs[kS * kD];
@@ -291,24 +331,33 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
   const uint16_t* dobase = dout + static_cast<int64_t>(b) * S * ors + h * kD;
   uint16_t* gbase = dqkv + static_cast<int64_t>(b) * S * rs + h * kD;
   const int q0 = w * 32, q = q0 + c;
-  const bool act = q0 < S;  // wave-uniform
-  int L = S;  // key bound
-  if constexpr (LEN) L = min(max(klen[b], 1), S);
+  int L = S;  // key bound (PACK: the query bound too)
+  if constexpr (LEN && !PACK) L = min(max(klen[b], 1), S);
+  int64_t row0 = 0;  // PACK: the sequence's first row
+  if constexpr (PACK) {
+    const PackRows pr = pack_rows(klen, b, S, T_);
+    L = pr.L, row0 = pr.row0;
+    if (L == 0) return;  // block-uniform, before any barrier
+    base = qkv + row0 * rs + h * kD, gbase = dqkv + row0 * rs + h * kD;
+    obase = o + row0 * ors + h * kD, dobase = dout + row0 * ors + h * kD;
+  }
+  const int QB = PACK ? L : S;  // query bound
+  const bool act = q0 < QB;  // wave-uniform
   // this lane's O / dO row halves and the row's log-sum-exp, loaded before the staging so their
   // latency overlaps it (Dq = rowsum(dO * O) is formed after the barrier)
-  const int qq = min(q, S - 1);
+  const int qq = min(q, QB - 1);
   u16x8 orow[4], drow[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     orow[j] = *reinterpret_cast<const u16x8*>(obase + static_cast<int64_t>(qq) * ors + 32 * hl + 8 * j);
     drow[j] = *reinterpret_cast<const u16x8*>(dobase + static_cast<int64_t>(qq) * ors + 32 * hl + 8 * j);
   }
-  const float lse_q = lse[static_cast<int64_t>(bh) * S + qq];
+  const float lse_q = PACK ? lse[static_cast<int64_t>(h) * T_ + row0 + qq] : lse[static_cast<int64_t>(bh) * S + qq];
   {
     uint16_t* const tt[3] = {Qs, Ks, dOs};
     const uint16_t* const ss[3] = {base, base + H * kD, dobase};
     const int64_t rr[3] = {rs, rs, ors};
-    const int nr[3] = {S, L, S};
+    const int nr[3] = {QB, L, QB};
     stage64n<3>(tt, ss, rr, nr);
   }
   __syncthreads();
@@ -336,8 +385,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           pt[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag<64>(Ks, kb * 32 + c, 2 * s + hl), qf[s], pt[kb], 0, 0, 0);
-          const bf16x8_t vf =
-              *reinterpret_cast<const bf16x8_t*>(base + 2 * H * kD + (kb * 32 + c) * rs + 16 * s + 8 * hl);
+          // PACK: row L of this sequence is not its own: clamped, the values are selected away below
+          const int vr = PACK ? min(kb * 32 + c, L - 1) : kb * 32 + c;
+          const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(base + 2 * H * kD + vr * rs + 16 * s + 8 * hl);
           ds[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, of[s], ds[kb], 0, 0, 0);
         }
         if constexpr (LEN) {  // pad keys: p = exp2(-huge) = 0 exactly, and dp = 0 whatever the V row holds
@@ -380,15 +430,16 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
       }
   }
   // P_drop -> T[q][key]: a lane's 4 consecutive keys of its query row per 8-B store (rows of idle
-  // waves' queries are zero)
+  // waves' queries are zero; PACK: so is every row >= L, whose lane computed on the clamped row L - 1)
+  const bool live = PACK ? q < L : act;
   auto put = [&](const f32x16 (&v)[4]) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const u16x4 x = act ? u16x4{f32_to_bf16(v[kb][4 * g]), f32_to_bf16(v[kb][4 * g + 1]),
-                                    f32_to_bf16(v[kb][4 * g + 2]), f32_to_bf16(v[kb][4 * g + 3])}
-                            : u16x4{0, 0, 0, 0};
+        const u16x4 x = live ? u16x4{f32_to_bf16(v[kb][4 * g]), f32_to_bf16(v[kb][4 * g + 1]),
+                                     f32_to_bf16(v[kb][4 * g + 2]), f32_to_bf16(v[kb][4 * g + 3])}
+                             : u16x4{0, 0, 0, 0};
         *reinterpret_cast<u16x4*>(T + off<128>(q, kb * 32 + 8 * g + 4 * hl)) = x;
       }
   };
@@ -396,9 +447,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
   __syncthreads();
   const int k0 = w * 32;
   const bool kact = LEN ? k0 < L : k0 < S;
-  const int nqs = S >> 4;  // 16-query steps
+  const int nqs = PACK ? (L + 15) >> 4 : S >> 4;  // 16-query steps
   uint16_t* krow = gbase + static_cast<int64_t>(k0 + c) * rs;
-  if constexpr (LEN) {
+  if constexpr (LEN && !PACK) {
     if (k0 >= L && k0 < S) {  // a fully padded key wave: dK = dV = 0 (dqkv is not pre-zeroed)
 #pragma unroll
       for (int t = 1; t < 3; ++t)
@@ -408,6 +459,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
   }
   auto store_t = [&](const f32x16 (&acc)[2], uint16_t* row, float mul) {
     // acc^T layout: lane column = key (or query) row of the output, rows d: 8-B pieces
+    if constexpr (PACK)
+      if (q >= L) return;  // q = k0 + c is the lane's key row as well: there is no row L to store
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -476,25 +529,29 @@ __global__ void attn_dropout_mask_kernel(uint8_t* __restrict__ mask, int64_t n, 
 
 }  // namespace
 
-// klen == nullptr: the unpadded (LEN = false) kernels
+// klen == nullptr: the unpadded (LEN = false) kernels; cu != nullptr: the packed ones (T rows in all)
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int S, int H, float scale, float p,
-                     uint64_t seed, hipStream_t s, const int32_t* klen) {
+                     uint64_t seed, hipStream_t s, const int32_t* klen, const int32_t* cu, int T) {
   const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 65536.0 + 0.5);
   const float rkeep = thr > 0 ? static_cast<float>(65536.0 / (65536.0 - thr)) : 1.f;  // 1 / (1 - p_eff)
   const dim3 grid(B * H);
-  auto* k = p > 0.f ? (klen ? attn_fwd_kernel<true, true> : attn_fwd_kernel<true, false>)
-                    : (klen ? attn_fwd_kernel<false, true> : attn_fwd_kernel<false, false>);
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, lse, S, H, scale, seed, thr, rkeep, klen);
+  auto* k = p > 0.f ? (klen ? attn_fwd_kernel<true, true, false> : attn_fwd_kernel<true, false, false>)
+                    : (klen ? attn_fwd_kernel<false, true, false> : attn_fwd_kernel<false, false, false>);
+  if (cu) k = p > 0.f ? attn_fwd_kernel<true, true, true> : attn_fwd_kernel<false, true, true>;
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, lse, S, H, scale, seed, thr, rkeep, cu ? cu : klen, T);
 }
 
 void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, uint16_t* dqkv,
-                     int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s, const int32_t* klen) {
+                     int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s, const int32_t* klen,
+                     const int32_t* cu, int T) {
   const uint32_t thr = static_cast<uint32_t>(static_cast<double>(p) * 65536.0 + 0.5);
   const float rkeep = thr > 0 ? static_cast<float>(65536.0 / (65536.0 - thr)) : 1.f;  // 1 / (1 - p_eff)
   const dim3 grid(B * H);
-  auto* k = p > 0.f ? (klen ? attn_bwd_kernel<true, true> : attn_bwd_kernel<true, false>)
-                    : (klen ? attn_bwd_kernel<false, true> : attn_bwd_kernel<false, false>);
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, dout, lse, dqkv, S, H, scale, seed, thr, rkeep, klen);
+  auto* k = p > 0.f ? (klen ? attn_bwd_kernel<true, true, false> : attn_bwd_kernel<true, false, false>)
+                    : (klen ? attn_bwd_kernel<false, true, false> : attn_bwd_kernel<false, false, false>);
+  if (cu) k = p > 0.f ? attn_bwd_kernel<true, true, true> : attn_bwd_kernel<false, true, true>;
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, qkv, out, dout, lse, dqkv, S, H, scale, seed, thr, rkeep,
+                     cu ? cu : klen, T);
 }
 
 void launch_attn_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, hipStream_t s) {

@@ -6,7 +6,8 @@ and counts match the published architectures -- BERT-base 110M (12 x 768, 12 hea
 3072, vocab 30522), Llama-3-8B 8.03B (32 x 4096, 32 q / 8 kv heads, FFN 14336, vocab
 128256, RoPE theta 500000).  BERT attention (S <= 128) runs the fused MFMA kernel of
 csrc/kernels/attention.hip (right-padded batches too: ``BertForMLM.forward(..., lengths=)``,
-``mlm_batch(..., lengths=)``), Llama's causal GQA attention the flash kernel of flash_attn.hip
+``mlm_batch(..., lengths=)``; or unpadded, the encoder on the valid tokens only: ``forward(..., seqs=)``,
+``mlm_batch(..., lengths=, packed=True)``), Llama's causal GQA attention the flash kernel of flash_attn.hip
 (packed rows too: ``LlamaForCausalLM.forward(..., doc_ids=)``, ``packed_lm_batch``);
 everything is bf16 on the GPU with fp32 masters on the parameter-server shards.
 """
@@ -23,8 +24,9 @@ from torch.utils.checkpoint import checkpoint
 
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
-from ..ops.transformer import (attention_causal_gqa, attention_qkv, cross_entropy, doc_bounds as _doc_bounds,
-                              layer_norm_residual, rms_norm, rope_split, rope_table, swiglu)
+from ..ops.transformer import (PackedSeqs, attention_causal_gqa, attention_qkv, cross_entropy,
+                              doc_bounds as _doc_bounds, layer_norm_residual, pack_seqs, rms_norm, rope_split,
+                              rope_table, swiglu)
 
 
 # ------------------------------------------------------------------------------------ BERT
@@ -53,13 +55,16 @@ class BertLayer(nn.Module):
         self.fc2 = SplitKLinear(c.ffn, c.hidden)
         self.ln2 = nn.LayerNorm(c.hidden, eps=c.eps)
 
-    def forward(self, x, mask: Optional[torch.Tensor] = None, key_lengths: Optional[torch.Tensor] = None):
+    def forward(self, x, mask: Optional[torch.Tensor] = None, key_lengths: Optional[torch.Tensor] = None,
+                seqs: Optional[PackedSeqs] = None):
+        """``seqs`` (ops.transformer.pack_seqs): ``x`` is [T, hidden], the valid tokens only -- every GEMM and
+        row kernel runs on T rows, attention reads sequence b at its offset."""
         p = self.c.dropout if self.training else 0.0
         # fused MFMA attention over the qkv projection for S <= 128 (ops/transformer.py), SDPA else;
         # key_lengths [B] (a right-padded batch) stays on the fused kernel, an arbitrary mask does not
         # fork: x's residual gradient is added inside the qkv / fc1 data-gradient GEMM (ops/dense.py)
         qkv, xr = self.qkv.fork(x)
-        a = attention_qkv(qkv, self.c.heads, p, mask, key_lengths)
+        a = attention_qkv(qkv, self.c.heads, p, mask, key_lengths, seqs)
         # post-LN epilogues: LN(x + dropout(sublayer)) as one fused HIP pass each way
         x = layer_norm_residual(xr, self.proj(a), self.ln1.weight, self.ln1.bias, self.c.eps, p, self.training)
         h, xr = self.fc1.fork(x)
@@ -90,7 +95,7 @@ class BertForMLM(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
-    def forward(self, ids, labels=None, positions=None, lengths=None):
+    def forward(self, ids, labels=None, positions=None, lengths=None, seqs: Optional[PackedSeqs] = None):
         """``positions`` [B, P] (the masked-LM positions of the original BERT pretraining input
         format, ``masked_lm_positions``): the LM head runs only on those B*P rows -- the vocab
         projection and its softmax are 1/(S/P) of the dense-head cost.  Without positions the
@@ -98,7 +103,19 @@ class BertForMLM(nn.Module):
 
         ``lengths`` [B] (any integer dtype): a right-padded batch -- tokens at or beyond
         ``lengths[b]`` of sequence b are padding that no token attends to (key lengths of every
-        layer's attention); their labels should be -100 (``mlm_batch(..., lengths=)``)."""
+        layer's attention); their labels should be -100 (``mlm_batch(..., lengths=)``).
+
+        ``seqs`` (``pack_seqs(lengths, S)``, ``mlm_batch(..., lengths=, packed=True)``; not with
+        ``lengths``): the same batch, unpadded -- ``ids`` / ``labels`` / ``positions`` keep their [B, S] /
+        [B, P] format, but the embeddings, every layer and the head run on the T valid tokens only.  With
+        ``positions`` the head rows are those positions (logits [B * P, V], as without ``seqs``); without
+        them the head runs on the T tokens and, with no ``labels``, the logits come back as [T, V] in
+        packed order (``ops.transformer.repad`` gives [B, S, V])."""
+        if seqs is not None:
+            if lengths is not None:
+                raise ValueError("BertForMLM: give lengths (padded) or seqs (unpadded), not both")
+            x, labels = self._encode_packed(ids, labels, positions, seqs)
+            return self._head(x, labels)
         b, s = ids.shape
         pos = torch.arange(s, device=ids.device)
         x = self.word(ids) + self.pos(pos)[None] + self.tok_type.weight[0]
@@ -115,14 +132,39 @@ class BertForMLM(nn.Module):
             x = x.reshape(b * s, -1).index_select(0, flat)
             if labels is not None:
                 labels = labels.reshape(-1).index_select(0, flat)
+        return self._head(x, labels)
+
+    def _head(self, x, labels):
         h = self.head_ln(F.gelu(self.head_dense(x)))
         logits = h @ self.word.weight.t() + self.head_bias
         if labels is None:
             return logits
         return cross_entropy(logits.view(-1, self.c.vocab), labels.reshape(-1), ignore_index=-100)
 
+    def _encode_packed(self, ids, labels, positions, seqs: PackedSeqs):
+        """The head's input rows and their labels from the T valid tokens of ``ids`` [B, S]."""
+        b, s = ids.shape
+        if (b, s) != (seqs.batch, seqs.seq):
+            raise ValueError("BertForMLM: ids [seqs.batch, seqs.seq]")
+        x = self.word(ids.reshape(-1).index_select(0, seqs.index)) + self.pos(seqs.pos) + self.tok_type.weight[0]
+        x = F.dropout(self.ln(x), self.c.dropout, self.training)  # [T, hidden]
+        for layer in self.layers:
+            x = layer(x, seqs=seqs)
+        if positions is not None:
+            # row of position (b, p) in the packed order; the clamp only moves the filler of a sequence
+            # masked in full, which mlm_batch points at a pad position (label -100)
+            cu = seqs.cu.long()
+            rows = (cu[:-1, None] + torch.minimum(positions, (cu[1:] - cu[:-1] - 1)[:, None])).reshape(-1)
+            x = x.index_select(0, rows)
+            if labels is not None:
+                flat = (positions + torch.arange(b, device=ids.device)[:, None] * s).reshape(-1)
+                labels = labels.reshape(-1).index_select(0, flat)
+        elif labels is not None:
+            labels = labels.reshape(-1).index_select(0, seqs.index)
+        return x, labels
 
-def _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions):
+
+def _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions, packed=False):
     """mlm_batch for a right-padded batch: ``ids`` are the full-length draws, ``g`` their generator."""
     batch, seq = ids.shape
     lens = torch.as_tensor(lengths, dtype=torch.int64).cpu()
@@ -144,28 +186,34 @@ def _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions):
     positions = torch.where(positions < seq, positions, filler)
     labels = torch.where(chosen, ids, torch.full_like(ids, -100))
     ids = ids.masked_fill(chosen, 103).masked_fill(pad, 0)  # [MASK], [PAD]
+    seqs = pack_seqs(lens, seq, device) if packed else None  # from the host lengths
     if device is not None:
         ids, labels, positions, lens = ids.to(device), labels.to(device), positions.to(device), lens.to(device)
-    return (ids, labels, positions, lens) if with_positions else (ids, labels, lens)
+    res = (ids, labels, positions, lens) if with_positions else (ids, labels, lens)
+    return res + (seqs,) if packed else res
 
 
 def mlm_batch(batch: int, seq: int, vocab: int = 30522, mask_prob: float = 0.15, seed: int = 0, device=None,
-              with_positions: bool = False, lengths=None):
+              with_positions: bool = False, lengths=None, packed: bool = False):
     """Synthetic MLM batch in the BERT pretraining format: exactly round(mask_prob * seq)
     masked positions per sequence (create_pretraining_data's num_to_predict), replaced by
     [MASK]; labels -100 elsewhere.  ``with_positions`` also returns masked_lm_positions [B, P].
 
     ``lengths`` (an int, or [batch] integers in [1, seq]) makes a right-padded batch and is returned
     last, as an int64 tensor: positions >= length hold id 0 ([PAD]) and label -100, and sequence b
-    masks max(1, round(mask_prob * length_b)) positions of [0, length_b).  ``positions`` stays
+    masks max(1, round(mask_prob * length_b)) positions of [0, length_b).  ``packed=True`` (with
+    ``lengths``) appends the batch's ``PackedSeqs`` for ``BertForMLM.forward(..., seqs=)`` as one more,
+    last, element.  ``positions`` stays
     rectangular at the batch maximum count: a shorter row is filled by repeating one of its valid
     unmasked positions (label -100, so the head ignores it; a sequence masked in full, such as one
     of length 1, repeats a pad position instead).  Without ``lengths`` the batch is what it always
     was for the seed."""
     g = torch.Generator().manual_seed(seed)
     ids = torch.randint(min(1000, vocab // 2), vocab, (batch, seq), generator=g)
+    if packed and lengths is None:
+        raise ValueError("mlm_batch: packed=True needs lengths")
     if lengths is not None:
-        return _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions)
+        return _mlm_batch_padded(ids, g, mask_prob, lengths, device, with_positions, packed)
     npred = max(1, int(round(mask_prob * seq)))
     positions = torch.rand(batch, seq, generator=g).argsort(dim=1)[:, :npred].sort(dim=1).values
     labels = torch.full_like(ids, -100)

@@ -7,6 +7,8 @@
   attention_qkv(qkv, H, p, mask, key_lengths) -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
                                                  projection (csrc/kernels/attention.hip, S <= 128;
                                                  right-padded batches by per-sequence key_lengths)
+  pack_seqs(lengths, seq) / unpad / repad     -> the valid tokens of a right-padded batch as [T, ...] rows;
+  attention_qkv(qkv [T, 3HD], H, p, seqs=)       attention reads sequence b at its offset (no pad rows)
   attention_causal_gqa(q, k, v, doc_bounds)   -> causal GQA flash attention, heads merged
                                                  (csrc/kernels/flash_attn.hip, head dim 128; packed
                                                  rows by per-token document bounds: doc_bounds(doc_ids))
@@ -16,6 +18,7 @@ runs the plain torch composition, which is also the numerics oracle in the GPU t
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -185,12 +188,75 @@ def attention_qkv_ok(qkv: torch.Tensor, heads: int, mask) -> bool:
             and knobs.enabled("fused_attn"))
 
 
+@dataclass(frozen=True)
+class PackedSeqs:
+    """The packing of a right-padded batch [B, seq] into its T = sum(lengths) valid tokens, in batch
+    order (``pack_seqs``).  ``cu`` int32 [B + 1] (exclusive prefix sum of the lengths), ``index`` int64
+    [T] (``b * seq + i`` of every valid token) and ``pos`` int64 [T] (its position ``i``) are on the
+    device; ``total`` (T), ``batch``, ``seq`` and ``max_len`` (the key bound the attention kernels run
+    with: max(lengths) rounded up to a multiple of 32) are Python ints."""
+    cu: torch.Tensor
+    index: torch.Tensor
+    pos: torch.Tensor
+    total: int
+    batch: int
+    seq: int
+    max_len: int
+
+
+def pack_seqs(lengths, seq: int, device=None) -> PackedSeqs:
+    """``lengths``: a list or a CPU integer tensor [B] with ``1 <= lengths[b] <= seq``.  It is read on
+    the host -- T sizes every later allocation, so it has to be known there without waiting for the
+    device; a CUDA tensor raises ``ValueError``.  The device tensors are uploaded ``non_blocking``."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda:
+            raise ValueError("pack_seqs: lengths on the host (a list or a CPU tensor) -- the token total sizes "
+                             "the packed tensors, and reading a CUDA tensor for it would sync the device")
+        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise ValueError("pack_seqs: integer lengths")
+    lens = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
+    seq = int(seq)
+    if lens.numel() < 1 or int(lens.min()) < 1 or int(lens.max()) > seq:
+        raise ValueError("pack_seqs: lengths is [B >= 1] integers in [1, seq]")
+    batch = lens.numel()
+    cu = torch.zeros(batch + 1, dtype=torch.int64)
+    torch.cumsum(lens, 0, out=cu[1:])
+    total = int(cu[-1])
+    if total >= 2 ** 31:
+        raise ValueError("pack_seqs: more than 2^31 - 1 tokens")
+    owner = torch.repeat_interleave(torch.arange(batch), lens)
+    pos = torch.arange(total) - cu[:-1][owner]
+    index = owner * seq + pos
+    up = lambda t: t if device is None else t.to(device, non_blocking=True)  # noqa: E731
+    return PackedSeqs(cu=up(cu.to(torch.int32)), index=up(index), pos=up(pos), total=total, batch=batch, seq=seq,
+                      max_len=(int(lens.max()) + 31) // 32 * 32)
+
+
+def unpad(x: torch.Tensor, seqs: PackedSeqs) -> torch.Tensor:
+    """[B, seq, ...] -> [T, ...]: the valid tokens in packed order (plain torch, differentiable)."""
+    if x.dim() < 2 or tuple(x.shape[:2]) != (seqs.batch, seqs.seq):
+        raise ValueError("unpad: x [batch, seq, ...] of the packing")
+    return x.reshape(seqs.batch * seqs.seq, *x.shape[2:]).index_select(0, seqs.index)
+
+
+def repad(x: torch.Tensor, seqs: PackedSeqs) -> torch.Tensor:
+    """[T, ...] -> [B, seq, ...] with zeros at the pad positions (plain torch, differentiable)."""
+    if x.dim() < 1 or x.shape[0] != seqs.total:
+        raise ValueError("repad: x [total, ...] of the packing")
+    z = x.new_zeros(seqs.batch * seqs.seq, *x.shape[1:])
+    return z.index_copy(0, seqs.index, x).view(seqs.batch, seqs.seq, *x.shape[1:])
+
+
 class _FusedAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, p, key_lengths):
+    def forward(ctx, qkv, heads, p, key_lengths, cu=None, max_len=0):
         qkv = qkv.contiguous()
         seed = _seed() if p > 0 else 0
-        if key_lengths is None:
+        ctx.max_len = int(max_len)
+        if cu is not None:  # packed: qkv [T, 3 * H * 64], sequence b at rows [cu[b], cu[b + 1])
+            out, lse = native().attn_fwd(qkv, heads, float(p), seed, None, cu, ctx.max_len)
+            ctx.save_for_backward(qkv, out, lse, cu)
+        elif key_lengths is None:
             out, lse = native().attn_fwd(qkv, heads, float(p), seed)
             ctx.save_for_backward(qkv, out, lse)
         else:
@@ -202,7 +268,11 @@ class _FusedAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, *klen = ctx.saved_tensors
-        return native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, *klen), None, None, None
+        if ctx.max_len:
+            return (native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, None, klen[0],
+                                      ctx.max_len), None, None, None, None, None)
+        return (native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, *klen),
+                None, None, None, None, None)
 
 
 def key_lengths_from_mask(mask: torch.Tensor) -> torch.Tensor:
@@ -229,8 +299,14 @@ def _device_key_lengths(key_lengths: torch.Tensor, qkv: torch.Tensor) -> torch.T
     return key_lengths.to(device=qkv.device, dtype=torch.int32, non_blocking=True).contiguous()
 
 
+def attention_packed_ok(qkv: torch.Tensor, heads: int, seqs: PackedSeqs) -> bool:
+    """The packed kernels' domain: GPU bf16, head dim 64, every sequence within 128 keys."""
+    return (_hip(qkv) and qkv.shape[1] == 3 * heads * 64 and seqs.max_len <= 128 and seqs.cu.device == qkv.device
+            and knobs.enabled("fused_attn"))
+
+
 def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[torch.Tensor] = None,
-                  key_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  key_lengths: Optional[torch.Tensor] = None, seqs: Optional[PackedSeqs] = None) -> torch.Tensor:
     """Multi-head self-attention over the fused projection ``qkv`` [B, S, 3 * H * D] (q | k | v,
     heads inner) -> [B, S, H * D], dropout ``p`` on the probabilities.  On the fused kernel the
     heads are never split into separate q / k / v tensors and the output is already merged.
@@ -238,12 +314,27 @@ def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[
     ``key_lengths`` [B] (any integer dtype) describes a right-padded batch: keys at or beyond
     ``clamp(key_lengths[b], 1, S)`` of sequence b take no part in any softmax, as under SDPA with a
     key-padding mask; every query row, padded ones included, is an ordinary row.  It stays in the
-    fused kernel's domain.  An arbitrary ``mask`` goes to SDPA; giving both raises ``ValueError``."""
+    fused kernel's domain.  An arbitrary ``mask`` goes to SDPA; giving both raises ``ValueError``.
+
+    ``seqs`` (``pack_seqs``; not with ``mask`` or ``key_lengths``): ``qkv`` is [T, 3 * H * D], the valid
+    tokens of a right-padded batch only, and the result is [T, H * D]; sequence b is rows
+    ``[cu[b], cu[b + 1])`` and attends to itself alone.  GPU bf16 with head dim 64 and
+    ``seqs.max_len <= 128`` runs the packed instantiations of the fused kernels, which read and write no
+    pad row at all; anything else is ``repad``, the ``key_lengths`` path above, ``unpad``."""
+    if seqs is not None:
+        if mask is not None or key_lengths is not None:
+            raise ValueError("attention_qkv: seqs describes the whole batch: no mask, no key_lengths")
+        if qkv.dim() != 2 or qkv.shape[0] != seqs.total:
+            raise ValueError("attention_qkv: packed qkv [seqs.total, 3 * heads * head_dim]")
+        if attention_packed_ok(qkv, heads, seqs):
+            return _FusedAttention.apply(qkv, heads, float(p), None, seqs.cu, seqs.max_len)
+        lens = seqs.cu[1:] - seqs.cu[:-1]
+        return unpad(attention_qkv(repad(qkv, seqs), heads, p, key_lengths=lens), seqs)
     if key_lengths is not None and mask is not None:
         raise ValueError("attention_qkv: give mask or key_lengths, not both")
     if attention_qkv_ok(qkv, heads, mask):
         klen = None if key_lengths is None else _device_key_lengths(key_lengths, qkv)
-        return _FusedAttention.apply(qkv, heads, float(p), klen)
+        return _FusedAttention.apply(qkv, heads, float(p), klen, None, 0)
     b, s, _ = qkv.shape
     if key_lengths is not None:
         klen = _device_key_lengths(key_lengths, qkv).clamp(1, s)
