@@ -923,11 +923,12 @@ std::vector<Tensor> layernorm_bwd(Tensor dy, Tensor s, Tensor gamma, Tensor mean
 }
 
 // Fused short-sequence attention (attention.hip): qkv [B, S, 3 * H * 64] -> [out [B, S, H * 64], lse [B, H, S]]
-static void check_attn(const Tensor& qkv, int64_t heads) {
+// max_s: 128 for the one-tile kernels, 512 for the chunked ones (attention_long.hip)
+static void check_attn(const Tensor& qkv, int64_t heads, int64_t max_s) {
   check_rows(qkv, "qkv");
   TORCH_CHECK(qkv.dim() == 3 && heads > 0 && qkv.size(2) == 3 * heads * 64, "qkv [B, S, 3 * heads * 64]");
   const int64_t S = qkv.size(1);
-  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= 128, "sequence length a multiple of 32, <= 128");
+  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= max_s, "sequence length a multiple of 32, <= ", max_s);
   TORCH_CHECK(qkv.size(0) * heads < (int64_t(1) << 31), "batch * heads");
 }
 
@@ -946,7 +947,8 @@ static const int32_t* attn_klen(const c10::optional<Tensor>& key_lengths, const 
 // -> [out [T, heads * 64], lse [heads, T]].  Only the layout is checked: the kernels clamp every sequence
 // into the T rows (looking at the values would be a host sync).  Returns nullptr without cu_seqlens.
 static const int32_t* attn_cu(const c10::optional<Tensor>& cu_seqlens, int64_t max_len,
-                              const c10::optional<Tensor>& key_lengths, const Tensor& qkv, int64_t heads) {
+                              const c10::optional<Tensor>& key_lengths, const Tensor& qkv, int64_t heads,
+                              int64_t max_s) {
   if (!cu_seqlens.has_value()) {
     TORCH_CHECK(max_len == 0, "max_len goes with cu_seqlens");
     return nullptr;
@@ -960,39 +962,44 @@ static const int32_t* attn_cu(const c10::optional<Tensor>& cu_seqlens, int64_t m
   TORCH_CHECK(cu.device() == qkv.device(), "cu_seqlens on qkv's device");
   TORCH_CHECK(cu.scalar_type() == torch::kInt32 && cu.is_contiguous() && cu.dim() == 1 && cu.numel() >= 2,
               "cu_seqlens int32, contiguous, [B + 1] with B >= 1");
-  TORCH_CHECK(max_len > 0 && max_len % 32 == 0 && max_len <= 128, "max_len a multiple of 32, <= 128");
+  TORCH_CHECK(max_len > 0 && max_len % 32 == 0 && max_len <= max_s, "max_len a multiple of 32, <= ", max_s);
   TORCH_CHECK((cu.numel() - 1) * heads < (int64_t(1) << 31), "batch * heads");
   return cu.data_ptr<int32_t>();
 }
 
-std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths,
-                             c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+using AttnFwdLaunch = decltype(&psamd::launch_attn_fwd);
+using AttnBwdLaunch = decltype(&psamd::launch_attn_bwd);
+
+static std::vector<Tensor> attn_fwd_any(AttnFwdLaunch launch, int64_t max_s, Tensor qkv, int64_t heads, double p,
+                                        int64_t seed, c10::optional<Tensor> key_lengths,
+                                        c10::optional<Tensor> cu_seqlens, int64_t max_len) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p in [0, 1)");
-  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads)) {
+  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads, max_s)) {
     const int64_t T = qkv.size(0), B = cu_seqlens->numel() - 1;
     const c10::DeviceGuard guard(qkv.device());
     auto out = torch::empty({T, heads * 64}, qkv.options());
     auto lse = torch::empty({heads, T}, qkv.options().dtype(torch::kFloat32));
-    psamd::launch_attn_fwd(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(max_len),
-                           static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed),
-                           cur_stream(qkv), nullptr, cu, static_cast<int>(T));
+    launch(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(max_len),
+           static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed), cur_stream(qkv),
+           nullptr, cu, static_cast<int>(T));
     return {out, lse};
   }
-  check_attn(qkv, heads);
+  check_attn(qkv, heads, max_s);
   const int64_t B = qkv.size(0), S = qkv.size(1);
   const int32_t* klen = attn_klen(key_lengths, qkv);
   const c10::DeviceGuard guard(qkv.device());
   auto out = torch::empty({B, S, heads * 64}, qkv.options());
   auto lse = torch::empty({B, heads, S}, qkv.options().dtype(torch::kFloat32));
-  psamd::launch_attn_fwd(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(S),
-                         static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed),
-                         cur_stream(qkv), klen);
+  launch(u16(qkv), u16m(out), lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(S),
+         static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed), cur_stream(qkv), klen,
+         nullptr, 0);
   return {out, lse};
 }
 
-Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed,
-                c10::optional<Tensor> key_lengths, c10::optional<Tensor> cu_seqlens, int64_t max_len) {
-  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads)) {
+static Tensor attn_bwd_any(AttnBwdLaunch launch, int64_t max_s, Tensor qkv, Tensor out, Tensor dout, Tensor lse,
+                           int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths,
+                           c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+  if (const int32_t* cu = attn_cu(cu_seqlens, max_len, key_lengths, qkv, heads, max_s)) {
     const int64_t T = qkv.size(0), B = cu_seqlens->numel() - 1;
     check_rows(out, "out");
     check_rows(dout, "dout");
@@ -1004,12 +1011,12 @@ Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, 
                 "packed lse fp32 [heads, T]");
     const c10::DeviceGuard guard(qkv.device());
     auto dqkv = torch::empty_like(qkv);
-    psamd::launch_attn_bwd(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B),
-                           static_cast<int>(max_len), static_cast<int>(heads), 0.125f, static_cast<float>(p),
-                           static_cast<uint64_t>(seed), cur_stream(qkv), nullptr, cu, static_cast<int>(T));
+    launch(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B),
+           static_cast<int>(max_len), static_cast<int>(heads), 0.125f, static_cast<float>(p),
+           static_cast<uint64_t>(seed), cur_stream(qkv), nullptr, cu, static_cast<int>(T));
     return dqkv;
   }
-  check_attn(qkv, heads);
+  check_attn(qkv, heads, max_s);
   const int64_t B = qkv.size(0), S = qkv.size(1);
   const int32_t* klen = attn_klen(key_lengths, qkv);
   check_rows(out, "out");
@@ -1021,10 +1028,31 @@ Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, 
               "lse fp32 [B, heads, S]");
   const c10::DeviceGuard guard(qkv.device());
   auto dqkv = torch::empty_like(qkv);
-  psamd::launch_attn_bwd(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B),
-                         static_cast<int>(S), static_cast<int>(heads), 0.125f, static_cast<float>(p),
-                         static_cast<uint64_t>(seed), cur_stream(qkv), klen);
+  launch(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), u16m(dqkv), static_cast<int>(B), static_cast<int>(S),
+         static_cast<int>(heads), 0.125f, static_cast<float>(p), static_cast<uint64_t>(seed), cur_stream(qkv), klen,
+         nullptr, 0);
   return dqkv;
+}
+
+std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double p, int64_t seed, c10::optional<Tensor> key_lengths,
+                             c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+  return attn_fwd_any(&psamd::launch_attn_fwd, 128, qkv, heads, p, seed, key_lengths, cu_seqlens, max_len);
+}
+Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed,
+                c10::optional<Tensor> key_lengths, c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+  return attn_bwd_any(&psamd::launch_attn_bwd, 128, qkv, out, dout, lse, heads, p, seed, key_lengths, cu_seqlens,
+                      max_len);
+}
+// The same calls on the chunked kernels (attention_long.hip): S or max_len a multiple of 32 up to 512
+std::vector<Tensor> attn_long_fwd(Tensor qkv, int64_t heads, double p, int64_t seed,
+                                  c10::optional<Tensor> key_lengths, c10::optional<Tensor> cu_seqlens,
+                                  int64_t max_len) {
+  return attn_fwd_any(&psamd::launch_attn_long_fwd, 512, qkv, heads, p, seed, key_lengths, cu_seqlens, max_len);
+}
+Tensor attn_long_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double p, int64_t seed,
+                     c10::optional<Tensor> key_lengths, c10::optional<Tensor> cu_seqlens, int64_t max_len) {
+  return attn_bwd_any(&psamd::launch_attn_long_bwd, 512, qkv, out, dout, lse, heads, p, seed, key_lengths,
+                      cu_seqlens, max_len);
 }
 
 // keep mask [B * H, S, S] (uint8) of the attention dropout for (p, seed) -- tests
@@ -2212,6 +2240,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none(), py::arg("cu_seqlens") = py::none(),
         py::arg("max_len") = 0);
   m.def("attn_dropout_mask", &attn_dropout_mask);
+  m.def("attn_long_fwd", &attn_long_fwd, py::arg("qkv"), py::arg("heads"), py::arg("p"), py::arg("seed"),
+        py::arg("key_lengths") = py::none(), py::arg("cu_seqlens") = py::none(), py::arg("max_len") = 0);
+  m.def("attn_long_bwd", &attn_long_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("heads"), py::arg("p"), py::arg("seed"), py::arg("key_lengths") = py::none(),
+        py::arg("cu_seqlens") = py::none(), py::arg("max_len") = 0);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_split_fwd", &rope_split_fwd);

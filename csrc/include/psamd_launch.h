@@ -579,6 +579,16 @@ void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
                      int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s,
                      const int32_t* klen = nullptr, const int32_t* cu = nullptr, int T = 0);
 void launch_attn_dropout_mask(uint8_t* mask, int64_t n, float p, uint64_t seed, hipStream_t s);
+// The same attention beyond one tile (attention_long.hip): S % 32 == 0, 32 <= S <= 512, online softmax
+// over 128-key chunks.  Arguments, layouts, length rules and the dropout draw of every element are those
+// of launch_attn_fwd / launch_attn_bwd at the same S; the results agree to rounding, not bitwise.  The
+// backward runs its dQ and its dK / dV kernel on s, in that order.
+void launch_attn_long_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int S, int H, float scale, float p,
+                          uint64_t seed, hipStream_t s, const int32_t* klen = nullptr, const int32_t* cu = nullptr,
+                          int T = 0);
+void launch_attn_long_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
+                          uint16_t* dqkv, int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s,
+                          const int32_t* klen = nullptr, const int32_t* cu = nullptr, int T = 0);
 // Causal GQA flash attention (flash_attn.hip): q [B, H, S, 128], k / v [B, KV, S, 128] bf16,
 // out [B, S, H * 128], lse / dsum [B, H, S] fp32; S % 128 == 0
 // Fused softmax cross-entropy over bf16 logits [R, V] (xent.hip): forward lse / per-row loss,

@@ -21,6 +21,7 @@
 // LDS tiles are row-major with a 16-B chunk XOR swizzle that keeps both access kinds conflict
 // free: direct ds_read_b128 fragments (16 rows, one chunk) and transposed ds_read_b64_tr_b16
 // fragments (4 consecutive rows x 64 B).
+#include "psamd_attn_dropout.h"
 #include "psamd_device.h"
 #include "psamd_launch.h"
 
@@ -72,24 +73,8 @@ __device__ __forceinline__ bf16x8_t tfrag(const uint16_t* T, int s, int c0, int 
   return __builtin_bit_cast(bf16x8_t, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-// one 32-bit hash per PAIR of elements (2j, 2j + 1): a 16-bit draw each, kept if >= p * 2^16.
-// The 64-bit seed folds into one 32-bit key (uniform: scalar ALU), so a pair costs ONE avalanche
-// finalizer (bijective in the pair index): the dropout hash had been the largest VALU item of the
-// fused attention kernels (two finalizers per pair, ~85 VALU per MFMA in the forward).
-__device__ __forceinline__ uint32_t pair_hash(uint64_t seed, uint32_t pair) {
-  const uint32_t k = static_cast<uint32_t>(seed) ^ (static_cast<uint32_t>(seed >> 32) * 0x9E3779B9u);
-  return mix32(pair ^ k);
-}
-__device__ __forceinline__ bool keep_lo(uint32_t h, uint32_t thr) { return (h & 0xffffu) >= thr; }
-__device__ __forceinline__ bool keep_hi(uint32_t h, uint32_t thr) { return (h >> 16) >= thr; }
+// mix32 / pair_hash / keep_lo / keep_hi (the dropout draw of element e) and pack_rows (the clamp of a
+// packed sequence) live in psamd_attn_dropout.h, shared with attention_long.hip
 
 __device__ __forceinline__ uint32_t pack2(float a, float b) {
   return pk_bf16(a, b);
@@ -151,17 +136,8 @@ __device__ __forceinline__ void stage64n(uint16_t* const (&T)[N], const uint16_t
 // runs with (max length rounded up to 32) and the S of the dropout element indices -- a packed call
 // draws the masks of the key-length call at that S.  Nothing is read or written at or beyond row L (the
 // next sequence's token, or the end of the allocation): loads clamp to row L - 1, stores are guarded.
-// L is clamped into [0, min(S, T)] and the base into [0, T - L], so no cu can leave the tensors.
-struct PackRows {
-  int64_t row0;
-  int L;
-};
-__device__ __forceinline__ PackRows pack_rows(const int32_t* __restrict__ cu, int b, int S, int T) {
-  const int c0 = cu[b], c1 = cu[b + 1];
-  const int64_t d = static_cast<int64_t>(c1) - c0;
-  const int L = static_cast<int>(min(max(d, int64_t{0}), static_cast<int64_t>(min(S, T))));
-  return {static_cast<int64_t>(min(max(c0, 0), T - L)), L};
-}
+// L is clamped into [0, min(S, T)] and the base into [0, T - L], so no cu can leave the tensors
+// (pack_rows, psamd_attn_dropout.h).
 
 // is accumulator element e of key block kb, on lane half hl, a key below L
 __device__ __forceinline__ bool key_ok(int kb, int e, int hl, int L) {

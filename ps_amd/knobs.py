@@ -33,7 +33,7 @@ ROUTES: Dict[str, str] = {
     "linear_fork": "linear weight gradients on the compute stream",
     "fused_relu": "Linear + ReLU as separate ops",
     "ps_linear": "PS-owned linear weight gradients through autograd's ordinary accumulation",
-    "fused_attn": "short-sequence attention on SDPA (key_lengths of a right-padded batch as a boolean key mask)",
+    "fused_attn": "BERT attention (S <= 512) on SDPA (key_lengths of a right-padded batch as a boolean key mask)",
     "flash_attn": "causal GQA attention on SDPA",
     "fused_xent": "cross-entropy on fp32 logits through F.cross_entropy",
     # sparse rows (ops/sparse.py)

@@ -4,8 +4,8 @@ checkpoints, no network).
 Compact in-repo definitions (transformers is not needed on the hot path): parameter shapes
 and counts match the published architectures -- BERT-base 110M (12 x 768, 12 heads, FFN
 3072, vocab 30522), Llama-3-8B 8.03B (32 x 4096, 32 q / 8 kv heads, FFN 14336, vocab
-128256, RoPE theta 500000).  BERT attention (S <= 128) runs the fused MFMA kernel of
-csrc/kernels/attention.hip (right-padded batches too: ``BertForMLM.forward(..., lengths=)``,
+128256, RoPE theta 500000).  BERT attention runs the fused MFMA kernels of
+csrc/kernels/attention.hip (S <= 128) and attention_long.hip (128 < S <= 512; S % 32 == 0) (right-padded batches too: ``BertForMLM.forward(..., lengths=)``,
 ``mlm_batch(..., lengths=)``; or unpadded, the encoder on the valid tokens only: ``forward(..., seqs=)``,
 ``mlm_batch(..., lengths=, packed=True)``), Llama's causal GQA attention the flash kernel of flash_attn.hip
 (packed rows too: ``LlamaForCausalLM.forward(..., doc_ids=)``, ``packed_lm_batch``);
@@ -60,7 +60,8 @@ class BertLayer(nn.Module):
         """``seqs`` (ops.transformer.pack_seqs): ``x`` is [T, hidden], the valid tokens only -- every GEMM and
         row kernel runs on T rows, attention reads sequence b at its offset."""
         p = self.c.dropout if self.training else 0.0
-        # fused MFMA attention over the qkv projection for S <= 128 (ops/transformer.py), SDPA else;
+        # fused MFMA attention over the qkv projection for S <= 128 (one tile) and 128 < S <= 512 (chunked),
+        # S % 32 == 0 (ops/transformer.py), SDPA else;
         # key_lengths [B] (a right-padded batch) stays on the fused kernel, an arbitrary mask does not
         # fork: x's residual gradient is added inside the qkv / fc1 data-gradient GEMM (ops/dense.py)
         qkv, xr = self.qkv.fork(x)

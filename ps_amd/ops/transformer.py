@@ -6,6 +6,7 @@
   rope_split(qkv, cs, H, KV)                  -> q, k, v  (RoPE + head split + transpose)
   attention_qkv(qkv, H, p, mask, key_lengths) -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
                                                  projection (csrc/kernels/attention.hip, S <= 128;
+                                                 csrc/kernels/attention_long.hip, 128 < S <= 512;
                                                  right-padded batches by per-sequence key_lengths)
   pack_seqs(lengths, seq) / unpad / repad     -> the valid tokens of a right-padded batch as [T, ...] rows;
   attention_qkv(qkv [T, 3HD], H, p, seqs=)       attention reads sequence b at its offset (no pad rows)
@@ -188,6 +189,22 @@ def attention_qkv_ok(qkv: torch.Tensor, heads: int, mask) -> bool:
             and knobs.enabled("fused_attn"))
 
 
+# The bounds the chunked kernels (csrc/kernels/attention_long.hip) are the default route within: the
+# bindings take S up to LONG_MAX_S anywhere; the route covers (SHORT_MAX_S, LONG_ROUTE_MAX_S], the
+# range where profiles/bert_attn_long_probe.txt shows them at or below the SDPA route's time.
+SHORT_MAX_S = 128
+LONG_MAX_S = 512
+LONG_ROUTE_MAX_S = 512
+
+
+def attention_long_ok(qkv: torch.Tensor, heads: int, mask) -> bool:
+    """The chunked kernels' domain on the default route: GPU bf16, head dim 64, S a multiple of 32 in
+    (128, LONG_ROUTE_MAX_S], no mask."""
+    return (mask is None and _hip(qkv) and qkv.dim() == 3 and qkv.shape[2] == 3 * heads * 64
+            and qkv.shape[1] % 32 == 0 and SHORT_MAX_S < qkv.shape[1] <= LONG_ROUTE_MAX_S
+            and knobs.enabled("fused_attn"))
+
+
 @dataclass(frozen=True)
 class PackedSeqs:
     """The packing of a right-padded batch [B, seq] into its T = sum(lengths) valid tokens, in batch
@@ -253,14 +270,17 @@ class _FusedAttention(torch.autograd.Function):
         qkv = qkv.contiguous()
         seed = _seed() if p > 0 else 0
         ctx.max_len = int(max_len)
+        # one tile (attention.hip) up to 128 keys, the chunked kernels (attention_long.hip) beyond
+        ctx.long = (ctx.max_len if cu is not None else qkv.shape[1]) > SHORT_MAX_S
+        fwd = native().attn_long_fwd if ctx.long else native().attn_fwd
         if cu is not None:  # packed: qkv [T, 3 * H * 64], sequence b at rows [cu[b], cu[b + 1])
-            out, lse = native().attn_fwd(qkv, heads, float(p), seed, None, cu, ctx.max_len)
+            out, lse = fwd(qkv, heads, float(p), seed, None, cu, ctx.max_len)
             ctx.save_for_backward(qkv, out, lse, cu)
         elif key_lengths is None:
-            out, lse = native().attn_fwd(qkv, heads, float(p), seed)
+            out, lse = fwd(qkv, heads, float(p), seed)
             ctx.save_for_backward(qkv, out, lse)
         else:
-            out, lse = native().attn_fwd(qkv, heads, float(p), seed, key_lengths)
+            out, lse = fwd(qkv, heads, float(p), seed, key_lengths)
             ctx.save_for_backward(qkv, out, lse, key_lengths)
         ctx.heads, ctx.p, ctx.seed = heads, float(p), seed
         return out
@@ -268,11 +288,11 @@ class _FusedAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, *klen = ctx.saved_tensors
+        bwd = native().attn_long_bwd if ctx.long else native().attn_bwd
         if ctx.max_len:
-            return (native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, None, klen[0],
-                                      ctx.max_len), None, None, None, None, None)
-        return (native().attn_bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, *klen),
-                None, None, None, None, None)
+            return (bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, None, klen[0], ctx.max_len),
+                    None, None, None, None, None)
+        return (bwd(qkv, out, dout.contiguous(), lse, ctx.heads, ctx.p, ctx.seed, *klen), None, None, None, None, None)
 
 
 def key_lengths_from_mask(mask: torch.Tensor) -> torch.Tensor:
@@ -305,6 +325,13 @@ def attention_packed_ok(qkv: torch.Tensor, heads: int, seqs: PackedSeqs) -> bool
             and knobs.enabled("fused_attn"))
 
 
+def attention_packed_long_ok(qkv: torch.Tensor, heads: int, seqs: PackedSeqs) -> bool:
+    """The packed chunked kernels' domain on the default route: GPU bf16, head dim 64, the longest sequence
+    (rounded up to 32) in (128, LONG_ROUTE_MAX_S]."""
+    return (_hip(qkv) and qkv.shape[1] == 3 * heads * 64 and SHORT_MAX_S < seqs.max_len <= LONG_ROUTE_MAX_S
+            and seqs.cu.device == qkv.device and knobs.enabled("fused_attn"))
+
+
 def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[torch.Tensor] = None,
                   key_lengths: Optional[torch.Tensor] = None, seqs: Optional[PackedSeqs] = None) -> torch.Tensor:
     """Multi-head self-attention over the fused projection ``qkv`` [B, S, 3 * H * D] (q | k | v,
@@ -314,25 +341,29 @@ def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[
     ``key_lengths`` [B] (any integer dtype) describes a right-padded batch: keys at or beyond
     ``clamp(key_lengths[b], 1, S)`` of sequence b take no part in any softmax, as under SDPA with a
     key-padding mask; every query row, padded ones included, is an ordinary row.  It stays in the
-    fused kernel's domain.  An arbitrary ``mask`` goes to SDPA; giving both raises ``ValueError``.
+    fused kernels' domain.  An arbitrary ``mask`` goes to SDPA; giving both raises ``ValueError``.
 
     ``seqs`` (``pack_seqs``; not with ``mask`` or ``key_lengths``): ``qkv`` is [T, 3 * H * D], the valid
     tokens of a right-padded batch only, and the result is [T, H * D]; sequence b is rows
     ``[cu[b], cu[b + 1])`` and attends to itself alone.  GPU bf16 with head dim 64 and
-    ``seqs.max_len <= 128`` runs the packed instantiations of the fused kernels, which read and write no
-    pad row at all; anything else is ``repad``, the ``key_lengths`` path above, ``unpad``."""
+    ``seqs.max_len <= 512`` runs the packed instantiations of the fused kernels, which read and write no
+    pad row at all; anything else is ``repad``, the ``key_lengths`` path above, ``unpad``.
+
+    The fused domain is S (or ``seqs.max_len``) a multiple of 32: up to 128 on the one-tile kernels
+    (attention.hip), from 160 to 512 on the chunked ones (attention_long.hip), with the same semantics,
+    layouts and dropout draw; S > 512, ``S % 32 != 0``, CPU, fp32 and PS_AMD_DISABLE=fused_attn take SDPA."""
     if seqs is not None:
         if mask is not None or key_lengths is not None:
             raise ValueError("attention_qkv: seqs describes the whole batch: no mask, no key_lengths")
         if qkv.dim() != 2 or qkv.shape[0] != seqs.total:
             raise ValueError("attention_qkv: packed qkv [seqs.total, 3 * heads * head_dim]")
-        if attention_packed_ok(qkv, heads, seqs):
+        if attention_packed_ok(qkv, heads, seqs) or attention_packed_long_ok(qkv, heads, seqs):
             return _FusedAttention.apply(qkv, heads, float(p), None, seqs.cu, seqs.max_len)
         lens = seqs.cu[1:] - seqs.cu[:-1]
         return unpad(attention_qkv(repad(qkv, seqs), heads, p, key_lengths=lens), seqs)
     if key_lengths is not None and mask is not None:
         raise ValueError("attention_qkv: give mask or key_lengths, not both")
-    if attention_qkv_ok(qkv, heads, mask):
+    if attention_qkv_ok(qkv, heads, mask) or attention_long_ok(qkv, heads, mask):
         klen = None if key_lengths is None else _device_key_lengths(key_lengths, qkv)
         return _FusedAttention.apply(qkv, heads, float(p), klen, None, 0)
     b, s, _ = qkv.shape
