@@ -536,8 +536,10 @@ void hash_slots(Tensor hkeys, Tensor ids, Tensor out, bool insert, Tensor status
 // (pre-filled with -1, power-of-two capacity >= 2x the old one) and its table row, flag and
 // state entries move to the new slot.  states are [cap, dim] or row-wise [cap].  remap [old cap]
 // receives the new slot of each old position (-1 = empty).
-void rehash_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor new_table, Tensor old_flags,
-                 Tensor new_flags, std::vector<Tensor> old_states, std::vector<Tensor> new_states, Tensor remap) {
+static psamd::RehashArgs rehash_args(const Tensor& old_hkeys, const Tensor& new_hkeys, const Tensor& old_table,
+                                     const Tensor& new_table, const Tensor& old_flags, const Tensor& new_flags,
+                                     const std::vector<Tensor>& old_states, const std::vector<Tensor>& new_states,
+                                     const Tensor& remap, bool growth_only) {
   check_i64(old_hkeys, "old_hkeys");
   check_i64(new_hkeys, "new_hkeys");
   check_i64(remap, "remap");
@@ -547,7 +549,7 @@ void rehash_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor ne
   check_gpu(new_flags, "new_flags");
   const int64_t oc = old_hkeys.numel(), nc = new_hkeys.numel();
   TORCH_CHECK(nc > 0 && (nc & (nc - 1)) == 0, "hash capacity must be a power of two");
-  TORCH_CHECK(nc >= 2 * oc, "rehash_rows: the new map must be at least twice the old one");
+  TORCH_CHECK(!growth_only || nc >= 2 * oc, "rehash_rows: the new map must be at least twice the old one");
   TORCH_CHECK(old_table.dim() == 2 && new_table.dim() == 2 && old_table.size(0) == oc && new_table.size(0) == nc &&
                   old_table.size(1) == new_table.size(1) && old_table.size(1) >= 1,
               "rehash_rows: tables [cap, dim]");
@@ -585,8 +587,99 @@ void rehash_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor ne
     a.st_full[i] = full ? 1 : 0;
   }
   a.remap = remap.data_ptr<int64_t>();
+  return a;
+}
+
+void rehash_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor new_table, Tensor old_flags,
+                 Tensor new_flags, std::vector<Tensor> old_states, std::vector<Tensor> new_states, Tensor remap) {
+  const psamd::RehashArgs a = rehash_args(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags,
+                                          old_states, new_states, remap, true);
   const c10::DeviceGuard guard(old_hkeys.device());
   psamd::launch_rehash_rows(a, cur_stream(old_hkeys));
+}
+
+static void check_stamp(const Tensor& t, int64_t n, const Tensor& like, const char* what) {
+  check_gpu(t, what);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.numel() == n && t.device() == like.device(), what,
+              ": int32 [cap] on the map's device");
+}
+
+// rehash_rows with a filter (eviction of expired rows): an old position moves iff its key is live
+// and old_stamp >= cutoff; its stamp moves too.  The target capacity is any power of two >= 64.
+// counters (int64 [2]) += {rows placed, rows evicted}; status (int32 [1]) is set if a survivor found
+// the target full (it then gets remap -1).
+void compact_rows(Tensor old_hkeys, Tensor new_hkeys, Tensor old_table, Tensor new_table, Tensor old_flags,
+                  Tensor new_flags, Tensor old_stamp, Tensor new_stamp, int64_t cutoff, Tensor counters,
+                  Tensor status, std::vector<Tensor> old_states, std::vector<Tensor> new_states, Tensor remap) {
+  psamd::RehashArgs a = rehash_args(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_states,
+                                    new_states, remap, false);
+  TORCH_CHECK(a.new_cap >= 64, "compact_rows: the new map needs at least 64 slots");
+  check_stamp(old_stamp, a.old_cap, old_hkeys, "old_stamp");
+  check_stamp(new_stamp, a.new_cap, old_hkeys, "new_stamp");
+  check_i64(counters, "counters");
+  check_gpu(status, "status");
+  TORCH_CHECK(counters.numel() == 2 && counters.device() == old_hkeys.device(), "counters int64 [2]");
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() >= 1 && status.device() == old_hkeys.device(),
+              "status int32 [1]");
+  TORCH_CHECK(cutoff >= INT32_MIN && cutoff <= INT32_MAX, "compact_rows: cutoff out of int32 range");
+  a.old_stamp = old_stamp.data_ptr<int32_t>();
+  a.new_stamp = new_stamp.data_ptr<int32_t>();
+  a.cutoff = static_cast<int32_t>(cutoff);
+  a.counters = counters.data_ptr<int64_t>();
+  a.status = status.data_ptr<int32_t>();
+  const c10::DeviceGuard guard(old_hkeys.device());
+  psamd::launch_compact_rows(a, cur_stream(old_hkeys));
+}
+
+// hash_slots with insert for expiring tables: also stamp[slot] = now for every resolved slot.
+// With ``table`` given, a key found with stamp < cutoff is reborn: row, flag and states of its slot
+// are zeroed, as in a slot that was never used.
+void hash_slots_stamp(Tensor hkeys, Tensor ids, Tensor out, Tensor stamp, int64_t now, int64_t cutoff,
+                      c10::optional<Tensor> table, c10::optional<Tensor> flags, std::vector<Tensor> states,
+                      Tensor status) {
+  check_i64(hkeys, "hkeys");
+  check_i64(ids, "ids");
+  check_i64(out, "out");
+  check_gpu(status, "status");
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() >= 1, "status int32 [1]");
+  const int64_t cap = hkeys.numel();
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0, "hash capacity must be a power of two");
+  TORCH_CHECK(out.numel() == ids.numel(), "out must match ids");
+  check_stamp(stamp, cap, hkeys, "stamp");
+  TORCH_CHECK(ids.device() == hkeys.device() && out.device() == hkeys.device() && status.device() == hkeys.device(),
+              "hash_slots_stamp: one device");
+  TORCH_CHECK(now >= 0 && now <= INT32_MAX && cutoff >= INT32_MIN && cutoff <= INT32_MAX,
+              "hash_slots_stamp: now / cutoff out of int32 range");
+  psamd::StampRebirth r{};
+  if (table.has_value()) {
+    TORCH_CHECK(flags.has_value(), "hash_slots_stamp: table and flags come together");
+    check_f32(*table, "table");
+    check_gpu(*flags, "flags");
+    TORCH_CHECK(table->dim() == 2 && table->size(0) == cap && table->size(1) >= 1 && table->device() == hkeys.device(),
+                "hash_slots_stamp: table [cap, dim]");
+    TORCH_CHECK(flags->scalar_type() == torch::kUInt8 && flags->numel() == cap && flags->device() == hkeys.device(),
+                "hash_slots_stamp: flags uint8 [cap]");
+    TORCH_CHECK(states.size() <= size_t(psamd::kRehashMaxState), "hash_slots_stamp: too many states");
+    r.table = table->data_ptr<float>();
+    r.flags = flags->data_ptr<uint8_t>();
+    r.dim = static_cast<int>(table->size(1));
+    r.nstate = static_cast<int>(states.size());
+    for (int i = 0; i < r.nstate; ++i) {
+      check_f32(states[i], "state");
+      const bool full = states[i].dim() == 2;
+      TORCH_CHECK(states[i].device() == hkeys.device() && states[i].size(0) == cap &&
+                      states[i].numel() == cap * (full ? r.dim : 1),
+                  "hash_slots_stamp: a state is [cap, dim] or [cap]");
+      r.st[i] = states[i].data_ptr<float>();
+      r.st_full[i] = full ? 1 : 0;
+    }
+  } else {
+    TORCH_CHECK(!flags.has_value() && states.empty(), "hash_slots_stamp: flags / states need the table");
+  }
+  const c10::DeviceGuard guard(ids.device());
+  psamd::launch_hash_slots_stamp(hkeys.data_ptr<int64_t>(), cap, ids.data_ptr<int64_t>(), ids.numel(),
+                                 out.data_ptr<int64_t>(), stamp.data_ptr<int32_t>(), static_cast<int32_t>(now),
+                                 static_cast<int32_t>(cutoff), r, status.data_ptr<int32_t>(), cur_stream(ids));
 }
 
 // ------------------------------------------------------------------------------ fused FC layer
@@ -2200,6 +2293,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row_base"), py::arg("lo"), py::arg("hi"), py::arg("keys") = py::none());
   m.def("hash_slots", &hash_slots);
   m.def("rehash_rows", &rehash_rows);
+  m.def("compact_rows", &compact_rows);
+  m.def("hash_slots_stamp", &hash_slots_stamp);
   m.def("unique_runs", &unique_runs);
   m.def("softmax_temp_fwd", &softmax_temp_fwd);
   m.def("softmax_temp_bwd", &softmax_temp_bwd);

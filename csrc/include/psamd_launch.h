@@ -173,8 +173,31 @@ struct RehashArgs {
   int nstate;
   int64_t* remap;
   int lg;
+  // compact_rows only (the filtered form): a position moves iff its key is live and
+  // old_stamp >= cutoff; counters = {rows placed, rows evicted} (added to); status is set when a
+  // survivor finds the target full
+  const int32_t* old_stamp;
+  int32_t* new_stamp;
+  int32_t cutoff;
+  int64_t* counters;
+  int32_t* status;
 };
 void launch_rehash_rows(const RehashArgs& a, hipStream_t s);
+// the same pass with the filter: new_cap is any power of two, smaller than old_cap included
+void launch_compact_rows(const RehashArgs& a, hipStream_t s);
+// hash_slots with insert that also writes stamp[slot] = now; with table != nullptr a key found
+// with stamp < cutoff has its slot reset to a fresh one's state (row, flag, states zero)
+struct StampRebirth {
+  float* table;
+  uint8_t* flags;
+  float* st[kRehashMaxState];
+  int st_full[kRehashMaxState];
+  int nstate;
+  int dim;
+};
+void launch_hash_slots_stamp(int64_t* hkeys, int64_t capacity, const int64_t* ids, int64_t n, int64_t* out,
+                             int32_t* stamp, int32_t now, int32_t cutoff, const StampRebirth& r, int32_t* status,
+                             hipStream_t s);
 
 // ---------------------------------------------------------------- fc.hip
 // fused FC backward: dW = (act'(y) * dy)^T x (+ db = column sums), dX = (act'(y) * dy) W;

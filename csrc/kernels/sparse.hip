@@ -23,6 +23,10 @@
 //                       tables keyed by unbounded ids; no host round trip per lookup
 //  rehash_rows          growth of such a map: one pass re-inserts every key into a larger map and
 //                       moves its row, flag and optimizer states to the new slot
+//  hash_slots_stamp     hash_slots for tables whose rows expire: stamps every resolved slot with the
+//                       table's round and resets a row found older than the cutoff
+//  compact_rows         rehash_rows with a filter: rows stamped before the cutoff stay behind, the
+//                       target map may be smaller (the reference never drops a row; see PARITY)
 #include <algorithm>
 
 #include "psamd_device.h"
@@ -457,6 +461,67 @@ void launch_hash_slots(int64_t* hkeys, int64_t capacity, const int64_t* ids, int
                      capacity - 1, ids, n, out, insert, status);
 }
 
+// hash_slots with insert for tables whose rows expire: every resolved slot also gets stamp[slot]
+// = now (the table's round).  Duplicate keys of one launch write the same value with plain
+// stores.  With rebirth targets (r.table != nullptr) a key found in the map whose stamp is older
+// than ``cutoff`` is a row nobody touched for too long: its slot is put back into the state of a
+// fresh one -- row, flag and states zero -- so the key behaves as a new row whether or not a
+// compaction has removed it in the meantime.  Several lanes may do that to one slot (they write
+// the same zeros); a slot claimed in this launch still holds the zeros it came with.
+__global__ __launch_bounds__(256) void hash_slots_stamp_kernel(unsigned long long* __restrict__ hkeys,
+                                                               int64_t cap_mask, const int64_t* __restrict__ ids,
+                                                               int64_t n, int64_t* __restrict__ out,
+                                                               int32_t* __restrict__ stamp, int32_t now, int32_t cutoff,
+                                                               const StampRebirth r, int32_t* __restrict__ status) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  const unsigned long long kEmpty = ~0ull;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned long long key = static_cast<unsigned long long>(ids[i]);
+    int64_t slot = -1;
+    bool claimed = false;
+    if (ids[i] >= 0) {
+      uint64_t h = mix_key(key) & static_cast<uint64_t>(cap_mask);
+      for (int64_t probe = 0; probe <= cap_mask; ++probe) {
+        unsigned long long cur = __hip_atomic_load(&hkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == key) { slot = static_cast<int64_t>(h); break; }
+        if (cur == kEmpty) {
+          const unsigned long long prev = atomicCAS(&hkeys[h], kEmpty, key);
+          if (prev == kEmpty || prev == key) { slot = static_cast<int64_t>(h); claimed = prev == kEmpty; break; }
+        }
+        h = (h + 1) & static_cast<uint64_t>(cap_mask);
+      }
+    }
+    out[i] = slot;
+    if (slot >= 0) {
+      if (r.table != nullptr && !claimed && stamp[slot] < cutoff) {
+        const int64_t o = slot * r.dim;
+        r.flags[slot] = 0;
+        for (int c = 0; c < r.dim; ++c) r.table[o + c] = 0.0f;
+        for (int s = 0; s < r.nstate; ++s) {
+          if (r.st_full[s]) {
+            for (int c = 0; c < r.dim; ++c) r.st[s][o + c] = 0.0f;
+          } else {
+            r.st[s][slot] = 0.0f;
+          }
+        }
+      }
+      stamp[slot] = now;
+    } else if (ids[i] >= 0) {
+      status[0] = 1;  // negative ids = pad keys (no row)
+    }
+  }
+}
+
+void launch_hash_slots_stamp(int64_t* hkeys, int64_t capacity, const int64_t* ids, int64_t n, int64_t* out,
+                             int32_t* stamp, int32_t now, int32_t cutoff, const StampRebirth& r, int32_t* status,
+                             hipStream_t s) {
+  if (n <= 0) return;
+  const int grid = stream_grid(n, 256);
+  hipLaunchKernelGGL(hash_slots_stamp_kernel, dim3(grid), dim3(256), 0, s,
+                     reinterpret_cast<unsigned long long*>(hkeys), capacity - 1, ids, n, out, stamp, now, cutoff, r,
+                     status);
+}
+
 // Growth of a map-mode shard: ONE pass over the old map re-inserts every live key into a larger,
 // empty key array (same mix_key / linear probing as hash_slots_kernel) and moves its payload --
 // table row, init flag, optimizer states -- to the new probe position.  A wave takes 64 old
@@ -468,7 +533,17 @@ void launch_hash_slots(int64_t* hkeys, int64_t capacity, const int64_t* ids, int
 // position p (-1 where p was empty) lets the host side translate slots it handed out before the
 // growth.  Every live row is read once and written once; destinations come zero-filled, so
 // untouched positions keep their meaning.
-template <bool VEC>
+//
+// FILTER (compact_rows): a position moves only if its key is live AND old_stamp >= cutoff; the
+// stamp moves with it, and the payload of an evicted position is never read.  The target may be
+// smaller than the source, so a survivor can find it full: the probe loop is bounded by the target
+// capacity, such a row gets remap -1 and sets ``status``.  counters[0] += rows placed, counters[1]
+// += rows evicted, counted from ballots: a wave sums the popcounts of its batches in a register,
+// the four waves of a block add up through LDS, and the block issues at most one integer atomic
+// per counter, so the sums do not depend on any order.  (One atomic per 64-position batch was
+// measured first: 2^15 batches hitting two addresses cost more than moving the rows, about 8 ns
+// each -- profiles/table_expiry_probe.txt has the figures after the change.)
+template <bool VEC, bool FILTER>
 __global__ __launch_bounds__(256) void rehash_rows_kernel(const RehashArgs a) {
   const int lane = threadIdx.x & 63;
   const int sub = lane >> a.lg;
@@ -480,12 +555,15 @@ __global__ __launch_bounds__(256) void rehash_rows_kernel(const RehashArgs a) {
   const uint64_t mask = static_cast<uint64_t>(a.new_cap - 1);
   const unsigned long long kEmpty = ~0ull;
   unsigned long long* nk = reinterpret_cast<unsigned long long*>(a.new_hkeys);
+  unsigned int nkept = 0, ngone = 0;  // FILTER: this wave's counts over all its batches (wave-uniform)
   for (int64_t base = wave * 64; base < a.old_cap; base += nwaves * 64) {  // wave-uniform
     const int64_t pl = base + lane;
     long long ql = -1;
+    bool evict = false;
     if (pl < a.old_cap) {
       const int64_t k = a.old_hkeys[pl];
-      if (k >= 0) {
+      if (FILTER && k >= 0) evict = a.old_stamp[pl] < a.cutoff;
+      if (k >= 0 && !evict) {
         const unsigned long long key = static_cast<unsigned long long>(k);
         uint64_t h = mix_key(key) & mask;
         for (int64_t probe = 0; probe < a.new_cap; ++probe) {
@@ -497,9 +575,16 @@ __global__ __launch_bounds__(256) void rehash_rows_kernel(const RehashArgs a) {
           a.new_flags[ql] = a.old_flags[pl];
           for (int s = 0; s < a.nstate; ++s)
             if (!a.st_full[s]) a.new_st[s][ql] = a.old_st[s][pl];
+          if (FILTER) a.new_stamp[ql] = a.old_stamp[pl];
+        } else if (FILTER) {
+          a.status[0] = 1;  // the target is full: a plain store, the host checks it at its next sync
         }
       }
       a.remap[pl] = ql;
+    }
+    if (FILTER) {  // every lane of the wave gets here
+      nkept += __popcll(__ballot(ql >= 0));
+      ngone += __popcll(__ballot(evict));
     }
     for (int j = 0; j < 64; j += per_wave) {
       const long long q = __shfl(ql, j + sub, kWave);  // every lane of the wave gets here
@@ -521,9 +606,23 @@ __global__ __launch_bounds__(256) void rehash_rows_kernel(const RehashArgs a) {
       }
     }
   }
+  if constexpr (FILTER) {  // (no thread left early: every one of the block's 256 gets here)
+    __shared__ unsigned int cnt[2][4];
+    if (lane == 0) {
+      cnt[0][threadIdx.x >> 6] = nkept;
+      cnt[1][threadIdx.x >> 6] = ngone;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      const unsigned long long t = static_cast<unsigned long long>(cnt[threadIdx.x][0]) + cnt[threadIdx.x][1] +
+                                   cnt[threadIdx.x][2] + cnt[threadIdx.x][3];
+      if (t) atomicAdd(reinterpret_cast<unsigned long long*>(a.counters) + threadIdx.x, t);
+    }
+  }
 }
 
-void launch_rehash_rows(const RehashArgs& a0, hipStream_t s) {
+template <bool FILTER>
+static void launch_rehash_impl(const RehashArgs& a0, hipStream_t s) {
   if (a0.old_cap <= 0) return;
   RehashArgs a = a0;
   bool vec = a.dim % 4 == 0 &&
@@ -538,10 +637,14 @@ void launch_rehash_rows(const RehashArgs& a0, hipStream_t s) {
   // positions at least twice and the inserts of one batch overlap the row traffic of another
   const int grid = stream_grid((a.old_cap + 1) / 2, 256);
   if (vec)
-    hipLaunchKernelGGL(rehash_rows_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((rehash_rows_kernel<true, FILTER>), dim3(grid), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL(rehash_rows_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((rehash_rows_kernel<false, FILTER>), dim3(grid), dim3(256), 0, s, a);
 }
+
+void launch_rehash_rows(const RehashArgs& a, hipStream_t s) { launch_rehash_impl<false>(a, s); }
+
+void launch_compact_rows(const RehashArgs& a, hipStream_t s) { launch_rehash_impl<true>(a, s); }
 
 // Compaction of sorted keys: for every run head i (i == 0 or srt[i] != srt[i-1]) with unique
 // index uidx[i] (inclusive scan of the head flags, minus 1): ukeys[u] = srt[i] & mask,

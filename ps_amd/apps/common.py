@@ -60,6 +60,9 @@ def connect(cfg: Config, device=None):
     from ..models.reference import local_table_factory, sharded_table_factory, tcp_table_factory
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if cfg.expire_rows < 0 or (cfg.expire_rows and not cfg.grow_rows):
+        raise ValueError("expire_rows=N (N >= 1 rounds) needs grow_rows=1: only growable tables evict rows")
+    expire = cfg.expire_rows or None
     if ctx.is_distributed() and world == 1:
         client = PSRouterClient(cfg.ps_addr_list)
         return client, tcp_table_factory(client, device, seed=cfg.seed)
@@ -75,8 +78,9 @@ def connect(cfg: Config, device=None):
             return tp, async_table_factory(tp, device, seed=cfg.seed,
                                            staleness=None if cons == "asp" else int(cfg.staleness))
         return tp, sharded_table_factory(tp, device, seed=cfg.seed, overlap=device is not None and
-                                         torch.device(device).type == "cuda", grow=cfg.grow_rows)
-    return None, local_table_factory(device, seed=cfg.seed, grow=cfg.grow_rows)
+                                         torch.device(device).type == "cuda", grow=cfg.grow_rows,
+                                         expire_after=expire)
+    return None, local_table_factory(device, seed=cfg.seed, grow=cfg.grow_rows, expire_after=expire)
 
 
 def make_trainer(cfg: Config, model, device=None, conn=None) -> Trainer:

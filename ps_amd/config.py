@@ -88,6 +88,7 @@ class Config:
     fault: str = ""  # e.g. "kill:rank=1:step=5", "delay_push:ms=50", "drop_push:p=0.01"
     heartbeat_s: float = 0.0
     grow_rows: bool = False  # map-mode sparse tables enlarge themselves (standalone / bsp ranks)
+    expire_rows: int = 0  # with grow_rows: drop rows untouched for more than this many rounds (0 = never)
 
     # ----------------------------------------------------------------- derived
     @property

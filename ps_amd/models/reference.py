@@ -37,28 +37,39 @@ from . import layers as L
 from .losses import CrossEntropy, Loss, SoftmaxLoss
 
 
-def local_table_factory(device=None, seed: int = 0, id_mode: str = "map", grow: bool = False):
+def local_table_factory(device=None, seed: int = 0, id_mode: str = "map", grow: bool = False,
+                        expire_after=None):
     """Standalone tables (one process holds every row).  ``grow``: map-mode tables enlarge
-    themselves when ``rows`` turns out too small (tables of another mode are fixed-size)."""
+    themselves when ``rows`` turns out too small (tables of another mode are fixed-size).
+    ``expire_after``: growable tables drop rows untouched for more than that many rounds."""
+    if expire_after and not grow:
+        raise ValueError("expire_after needs grow=True: only growable tables evict rows")
+
     def make(name, dim, rows, init, mode=None, fields=1):
         m = mode or id_mode
         return SparseTable(name, dim, rows, init=init, id_mode=m, seed=stable_seed(name, seed),
-                           device=device, fields=fields, grow=grow and m == "map")
+                           device=device, fields=fields, grow=grow and m == "map",
+                           expire_after=(expire_after or None) if grow and m == "map" else None)
 
     return make
 
 
 def sharded_table_factory(transport, device=None, seed: int = 0, id_mode: str = "map", overlap: bool = True,
-                          exchange=None, grow: bool = False):
+                          exchange=None, grow: bool = False, expire_after=None):
     """Rows partitioned over the co-located servers of ``transport`` (torchrun ranks); with
     ``overlap`` (GPU) row gradients are pushed from backward hooks on a side stream.
     ``exchange``: "plane" | "collective" | None (auto, see row_plane.plane_rows_wanted).
-    ``grow``: map-mode tables enlarge their shards on demand (collective exchange only)."""
+    ``grow``: map-mode tables enlarge their shards on demand (collective exchange only);
+    ``expire_after``: such tables drop rows untouched for more than that many rounds."""
+    if expire_after and not grow:
+        raise ValueError("expire_after needs grow=True: only growable tables evict rows")
+
     def make(name, dim, rows, init, mode=None, fields=1):
         m = mode or id_mode
         return ShardedSparseTable(name, dim, rows, transport, init=init, id_mode=m,
                                   seed=stable_seed(name, seed), device=device, fields=fields, overlap=overlap,
-                                  exchange=exchange, grow=grow and m == "map")
+                                  exchange=exchange, grow=grow and m == "map",
+                                  expire_after=(expire_after or None) if grow and m == "map" else None)
 
     return make
 

@@ -319,6 +319,73 @@ def rehash_rows(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags
     return rehash_rows_ref(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_states, new_states)
 
 
+def hash_slots_stamp(hkeys: torch.Tensor, ids: torch.Tensor, stamp: torch.Tensor, now: int, status: torch.Tensor, *,
+                     cutoff: int | None = None, table: torch.Tensor | None = None,
+                     flags: torch.Tensor | None = None, states=()) -> torch.Tensor:
+    """``hash_slots`` with insert for tables whose rows expire (HIP kernel, GPU only): also
+    ``stamp[slot] = now`` (int32 [capacity]) for every resolved slot; pad keys stamp nothing.
+    With ``cutoff`` (and ``table`` / ``flags`` / ``states``) a key found with ``stamp < cutoff`` is
+    reborn: row, flag and states of its slot are zeroed, the state of a slot never used."""
+    out = torch.empty_like(ids)
+    if cutoff is None:
+        native().hash_slots_stamp(hkeys, ids.contiguous(), out, stamp, int(now), -(1 << 31), None, None, [], status)
+    else:
+        native().hash_slots_stamp(hkeys, ids.contiguous(), out, stamp, int(now), max(int(cutoff), -(1 << 31)), table,
+                                  flags, list(states), status)
+    return out
+
+
+def _check_compact_cap(new_cap: int) -> None:
+    if new_cap < 64 or new_cap & (new_cap - 1):
+        raise ValueError(f"compact_rows: the new map needs a power-of-two capacity >= 64 (got {new_cap})")
+
+
+def compact_rows_ref(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_stamp, new_stamp,
+                     cutoff, counters, status, old_states=(), new_states=()):
+    """Oracle of ``compact_rows`` as a composition: the keys of expired positions are masked to
+    -1, the rest inserted into the new map (``hash_slots`` on the GPU, the host model of the same
+    probing on CPU tensors), then masked index copies.  A survivor that finds the map full gets
+    remap -1 and sets ``status``."""
+    _check_compact_cap(new_hkeys.numel())
+    live = old_hkeys >= 0
+    keep = live & (old_stamp >= int(cutoff))
+    masked = torch.where(keep, old_hkeys, torch.full_like(old_hkeys, -1))
+    if old_hkeys.is_cuda:
+        remap = hash_slots(new_hkeys, masked, True, status)
+    else:
+        remap = _probe_insert_cpu(new_hkeys, masked)
+        if bool(((remap < 0) & keep).any()):
+            status[0] = 1
+    src = torch.nonzero(remap >= 0).reshape(-1)
+    dst = remap[src]
+    new_table[dst] = old_table[src]
+    new_flags[dst] = old_flags[src]
+    new_stamp[dst] = old_stamp[src]
+    for o, n in zip(old_states, new_states):
+        n[dst] = o[src]
+    counters += torch.stack([(remap >= 0).sum(), (live & ~keep).sum()]).to(counters.dtype)
+    return remap
+
+
+def compact_rows(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_stamp, new_stamp, cutoff,
+                 counters, status, old_states=(), new_states=()):
+    """``rehash_rows`` with a filter (HIP on the GPU): an old position moves iff its key is live and
+    ``old_stamp >= cutoff`` -- key, row, flag, states and stamp; the payload of an evicted position
+    is not read.  ``new_hkeys`` (pre-filled with -1; the other ``new_*`` zero-filled) has any
+    power-of-two capacity >= 64, smaller than the old one included; the caller sizes it so that the
+    survivors fill at most half.  ``counters`` int64 [2] += (rows placed, rows evicted);
+    ``status`` int32 [1] is set if a survivor found the map full.  -> remap [old cap]: the new slot,
+    -1 for empty, evicted and unplaced positions."""
+    _check_compact_cap(new_hkeys.numel())
+    if use_native(old_table, old_hkeys):
+        remap = torch.empty_like(old_hkeys)
+        native().compact_rows(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_stamp, new_stamp,
+                              int(cutoff), counters, status, list(old_states), list(new_states), remap)
+        return remap
+    return compact_rows_ref(old_hkeys, new_hkeys, old_table, new_table, old_flags, new_flags, old_stamp, new_stamp,
+                            cutoff, counters, status, old_states, new_states)
+
+
 class _GatherUnique(torch.autograd.Function):
     """out[k] = leaf[inv[k]] (cast to out_dtype); backward = deterministic segment sum of the
     output gradient per unique row (sorted-order perm + seg_off), no atomics, no sort."""

@@ -100,7 +100,10 @@ class AsyncRowTable(TcpSparseTable):
                  updater: Optional[Updater] = None, *, init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "map",
                  seed: int = 0, fields: int = 1, device=None, staleness: Optional[int] = None,
                  capacity: int = 1 << 15, rows_per_owner: Optional[int] = None, timeout_s: float = 600.0,
-                 grow: bool = False):
+                 grow: bool = False, expire_after: Optional[int] = None):
+        if expire_after is not None:  # eviction is a rehash of a growable shard
+            raise ValueError("AsyncRowTable does not support expire_after: its owner thread serves the shard's "
+                             "tensors in place, so rows cannot be compacted away (expiring tables need bsp)")
         if grow:  # the native owner thread holds raw pointers into the shard (set_shard)
             raise ValueError("AsyncRowTable does not support grow=True: its owner thread serves the shard's "
                              "tensors in place; size it with rows_per_owner (growable tables need bsp)")

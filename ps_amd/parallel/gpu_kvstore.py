@@ -298,10 +298,11 @@ class GpuKVStore:
     # ------------------------------------------------------------------ sparse rows
     def add_table(self, name: str, dim: int, rows: Union[int, Sequence[int]], updater: Optional[Updater] = None, *,
                   init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "map", seed: int = 0, fields: int = 1,
-                  grow: bool = False):
+                  grow: bool = False, expire_after: Optional[int] = None):
         """A row-sparse table on the same ranks (collective).  Rows are created lazily on first
         pull with a deterministic init keyed by the global row key.  ``grow`` (bsp, map mode):
-        the owners enlarge their shards when ``rows`` turns out too small."""
+        the owners enlarge their shards when ``rows`` turns out too small; ``expire_after`` (with
+        ``grow``): they drop rows that no pull touched for more than that many rounds."""
         if name in self.tables:
             raise KeyError(f"table {name!r} exists")
         from .sparse_table import stable_seed
@@ -310,13 +311,15 @@ class GpuKVStore:
             from .sparse_table import ShardedSparseTable
 
             tab = ShardedSparseTable(name, dim, rows, self.t, updater, init=init, id_mode=id_mode,
-                                     seed=stable_seed(name, seed), device=self.device, fields=fields, grow=grow)
+                                     seed=stable_seed(name, seed), device=self.device, fields=fields, grow=grow,
+                                     expire_after=expire_after)
         else:
             from .async_rows import AsyncRowTable
 
             tab = AsyncRowTable(name, dim, rows, self.t, updater, init=init, id_mode=id_mode,
                                 seed=stable_seed(name, seed), device=self.device, fields=fields,
-                                staleness=None if self.consistency == "asp" else self.staleness, grow=grow)
+                                staleness=None if self.consistency == "asp" else self.staleness, grow=grow,
+                                expire_after=expire_after)
         self.tables[name] = tab
         return tab
 

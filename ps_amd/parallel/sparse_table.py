@@ -41,6 +41,13 @@ exchange instead of one getList per field:
   translated.  ``GrowthPolicy`` decides from host bookkeeping and asynchronous live counts, so
   steady state stays host-sync-free.  W = 1 and the collective exchange; not the row plane.
 
+* expiry   (``grow=True`` and ``expire_after=N``) the other half of lazy creation: every lookup stamps
+  the rows it resolves with the table's ``round``; a row whose stamp is more than N rounds old is
+  expired, and its id, should it return, is a new row (deterministic init, zero optimizer state).
+  The owner gets the memory back by compaction (``compact_rows``): the rehash of growth with the
+  expired rows left out, into a map sized for the survivors -- decided by ``GrowthPolicy`` at the
+  load where a plain growable map would double, or asked for with ``evict()``.
+
 * bags     ``lookup_bags(values, offsets)``: a multi-hot field holds a list of ids and its vector is
   the sum / mean / weighted sum of their rows.  Keys, plan, exchange, push and growth are those of
   ``lookup``; between the pulled unique rows and the model the gather is replaced by the fused HIP
@@ -153,27 +160,52 @@ class GrowthPolicy:
     insert -> the capacity to grow to, or None; ``launched(n)`` after it -> True when a snapshot
     should be enqueued now (stream order makes it include that lookup's inserts).  ``poll()``
     returns the count of the snapshot in flight if it has landed, else None; ``wait()`` blocks
-    for it.  At most one snapshot is in flight."""
+    for it.  At most one snapshot is in flight.
 
-    def __init__(self, cap: int, live: int = 0):
+    ``expiring`` (tables with ``expire_after``): a snapshot is the pair (live, fresh), fresh = the
+    keys whose stamp was not below the cutoff when the snapshot was enqueued.  The cutoff only
+    rises, so the survivors of any later compaction are among those keys and the keys looked up
+    since: ``fresh_bound = fresh_snap + since`` never underestimates them.  At the hard load the
+    decision is a compaction into ``max(64, pow2(4 * (fresh_bound + n)))`` slots -- fewer, as many
+    or more than now.  After it the survivors are all that is live, so ``fresh_snap`` takes the
+    place of ``live_snap``; a snapshot in flight describes the old map and is dropped (its owner
+    forgets it too), and ``launched`` asks for a new one whatever the load."""
+
+    def __init__(self, cap: int, live: int = 0, expiring: bool = False):
         self.cap, self.live_snap, self.since = int(cap), int(live), 0
         self.in_flight = False
         self._mark = 0  # ``since`` when the snapshot in flight was enqueued
         self.waits = 0
         self.grows = 0
+        self.expiring = bool(expiring)
+        self.fresh_snap = int(live)
+        self.compactions = 0
+        self._resnap = False  # a compaction dropped what the snapshots said: take one at once
 
     @property
     def bound(self) -> int:
         return self.live_snap + self.since
 
+    @property
+    def fresh_bound(self) -> int:
+        return self.fresh_snap + self.since
+
     def _over(self, n: int, load: Tuple[int, int]) -> bool:
         return (self.bound + n) * load[1] > self.cap * load[0]
 
-    def _fold(self, live: int) -> None:
+    def _fold(self, live) -> None:
+        if self.expiring:
+            live, fresh = live
+            self.fresh_snap = int(fresh)
         self.live_snap = int(live)
         self.since -= self._mark
         self._mark = 0
         self.in_flight = False
+
+    def reset(self, cap: int, live: int) -> None:
+        """The owner counted the live keys exactly (an explicit eviction, a loaded checkpoint)."""
+        self.cap, self.live_snap, self.fresh_snap, self.since = int(cap), int(live), int(live), 0
+        self.in_flight, self._mark, self._resnap = False, 0, False
 
     def admit(self, n: int, poll: Optional[Callable] = None, wait: Optional[Callable] = None) -> Optional[int]:
         if self.in_flight:
@@ -185,14 +217,22 @@ class GrowthPolicy:
             self._fold(wait())
         if not self._over(n, GROW_HARD_LOAD):
             return None
+        if self.expiring:
+            cap = max(64, _pow2((self.fresh_bound + n) * GROW_TARGET_LOAD[1] // GROW_TARGET_LOAD[0]))
+            self.grows += cap > self.cap
+            self.compactions += 1
+            self.cap, self.live_snap = cap, self.fresh_snap  # bound == fresh_bound: the survivors' bound
+            self.in_flight, self._mark, self._resnap = False, 0, True
+            return cap
         self.cap = _pow2((self.bound + n) * GROW_TARGET_LOAD[1] // GROW_TARGET_LOAD[0])
         self.grows += 1
         return self.cap
 
     def launched(self, n: int) -> bool:
         self.since += int(n)
-        if self.in_flight or not self._over(0, GROW_SOFT_LOAD):
+        if self.in_flight or not (self._resnap or self._over(0, GROW_SOFT_LOAD)):
             return False
+        self._resnap = False
         self.in_flight = True
         self._mark = self.since
         return True
@@ -203,10 +243,16 @@ class RowShard:
     (map mode) the key -> slot map -- a device hash map on the GPU, the native IdMap on CPU.
     With ``grow`` (map mode) the shard enlarges itself instead of running full: ``on_grow(remap)``
     is called after every growth (``remap``: old slot -> new slot on the GPU, None on the CPU,
-    where slots are insertion-ordered and stay)."""
+    where slots are insertion-ordered and stay).
+
+    With ``expire_after`` = N (growable shards) every lookup with insert stamps the slots it resolves
+    with the owner's round ``now``, and a row is expired once ``stamp < now - N``.  A lookup that
+    finds an expired row resets its slot to a fresh one's state, so a key that comes back is a new
+    row whether or not a compaction removed it in between; ``compact`` is what gives the memory
+    back: a rehash that leaves the expired rows out (slots move on both devices -> remap)."""
 
     def __init__(self, dim: int, capacity: int, mode: str, row_base: int, seed: int, init: Tuple[float, float],
-                 device, updater: Optional[Updater], grow: bool = False):
+                 device, updater: Optional[Updater], grow: bool = False, expire_after: Optional[int] = None):
         self.dim, self.mode, self.row_base, self.seed = int(dim), mode, int(row_base), int(seed)
         self.init = init
         self.device = device
@@ -224,9 +270,22 @@ class RowShard:
         if grow and mode != "map":
             raise ValueError("grow=True needs id_mode='map'")
         self.growable = bool(grow)
+        if expire_after is not None:
+            if not self.growable:
+                raise ValueError("expire_after needs grow=True: eviction is a rehash of a growable map-mode shard")
+            if int(expire_after) < 1:
+                raise ValueError(f"expire_after must be >= 1 round (got {expire_after}): a row pulled in this "
+                                 "round still waits for its push")
+        self.expire_after = int(expire_after) if expire_after is not None else 0
         self.on_grow: Optional[Callable] = None
         self.stats = {"host_syncs": 0}  # the owning table shares its own dict
-        self._pol = GrowthPolicy(self.capacity) if self.growable and self.gpu else None
+        self._pol = GrowthPolicy(self.capacity, expiring=bool(self.expire_after)) if self.growable and self.gpu \
+            else None
+        self.stamp: Optional[torch.Tensor] = None
+        if self.expire_after:
+            self.stamp = torch.zeros(self.capacity, dtype=torch.int32, device=device)
+            self.counters = torch.zeros(2, dtype=torch.int64, device=device)  # rows (kept, evicted) by compactions
+            self._cutoff = -(1 << 31)  # of the latest lookup: only rises
         self._snap: Optional[Tuple[torch.Tensor, object]] = None  # (pinned count, event) in flight
         self.status = torch.zeros(1, dtype=torch.int32, device=device)  # map miss / overflow flag
         self.table = torch.zeros(self.capacity, self.dim, dtype=torch.float32, device=device)
@@ -243,9 +302,12 @@ class RowShard:
         else:
             self.states = [torch.zeros_like(self.table) for _ in range(u.n_state)]
 
-    def slots(self, keys: torch.Tensor, insert: bool = True) -> torch.Tensor:
+    def slots(self, keys: torch.Tensor, insert: bool = True, now: int = 0) -> torch.Tensor:
+        """Slots of ``keys``; ``now``: the owner's round, the stamp of an expiring shard's lookups."""
         if self.mode != "map":
             return keys - self.row_base
+        if insert and self.expire_after:
+            return self._slots_stamped(keys, int(now))
         if self.gpu:
             if not (insert and self.growable):
                 return _sp.hash_slots(self.hkeys, keys, insert, self.status)
@@ -264,27 +326,117 @@ class RowShard:
             raise RuntimeError(f"sparse table shard full ({self.capacity} rows)")
         return s
 
+    def _slots_stamped(self, keys: torch.Tensor, now: int) -> torch.Tensor:
+        """Lookup with insert on an expiring shard: compact first if the map would pass its load,
+        then resolve, reset the expired rows among the resolved ones, and stamp."""
+        n = keys.numel()
+        cutoff = self._cutoff = max(self._cutoff, now - self.expire_after)
+        if self.gpu:
+            new_cap = self._pol.admit(n, self._snap_poll, self._snap_wait)
+            if new_cap is not None:
+                self.compact(new_cap, cutoff)
+            out = _sp.hash_slots_stamp(self.hkeys, keys, self.stamp, now, self.status, cutoff=cutoff,
+                                       table=self.table, flags=self.flags, states=self.states)
+            if self._pol.launched(n):
+                self._snap_enqueue()
+            return out
+        if len(self.idmap) + n > self.capacity:
+            self.compact(max(64, 2 * (self.count_fresh(cutoff) + n)), cutoff)
+        s = self.idmap.lookup(keys, True).to(keys.device)
+        if bool((s < 0).any()):
+            raise RuntimeError(f"sparse table shard full ({self.capacity} rows)")
+        reborn = s[self.stamp[s] < cutoff]  # (a slot created just now holds zeros already)
+        if reborn.numel():
+            self.table[reborn], self.flags[reborn] = 0.0, 0
+            for st in self.states:
+                st[reborn] = 0.0
+        self.stamp[s] = now
+        return s
+
     # ---- growth (map mode): the live-count snapshot is the pattern of ShardedSparseTable._route
     def _snap_enqueue(self) -> None:
-        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
-        host.copy_((self.hkeys != -1).sum().reshape(1), non_blocking=True)
+        live = self.hkeys != -1
+        if self.expire_after:  # (live, fresh): fresh by the cutoff of the lookup just launched
+            cnt = torch.stack([live.sum(), (live & (self.stamp >= self._cutoff)).sum()])
+        else:
+            cnt = live.sum().reshape(1)
+        host = torch.empty(cnt.numel(), dtype=torch.int64, pin_memory=True)
+        host.copy_(cnt, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._snap = (host, ev)
 
-    def _snap_poll(self) -> Optional[int]:
+    def _snap_value(self, host: torch.Tensor):
+        return (int(host[0]), int(host[1])) if self.expire_after else int(host[0])
+
+    def _snap_poll(self):
         host, ev = self._snap
         if not ev.query():
             return None
         self._snap = None
-        return int(host[0])
+        return self._snap_value(host)
 
-    def _snap_wait(self) -> int:
+    def _snap_wait(self):
         host, ev = self._snap
         self.stats["host_syncs"] += 1
         ev.synchronize()
         self._snap = None
-        return int(host[0])
+        return self._snap_value(host)
+
+    def count_fresh(self, cutoff: int) -> int:
+        """Exact number of live rows with stamp >= cutoff (GPU: one counted host sync)."""
+        if self.gpu:
+            self.stats["host_syncs"] += 1
+            return int(((self.hkeys != -1) & (self.stamp >= int(cutoff))).sum().item())
+        live = self.idmap.items()[:, 1]
+        return int((self.stamp[live] >= int(cutoff)).sum())
+
+    def compact(self, new_cap: int, cutoff: int, live: Optional[int] = None) -> torch.Tensor:
+        """Move the rows with ``stamp >= cutoff`` into a fresh shard of ``new_cap`` slots (fewer, as
+        many or more than now) and drop the others -> remap [old capacity], -1 for empty and
+        evicted positions.  GPU: one ``compact_rows`` pass on the current stream.  CPU: the
+        survivors keep their insertion order in the rebuilt id map.  ``live``: the survivor count
+        where the caller knows it exactly.  A local decision of this owner: no collective."""
+        if not self.expire_after:
+            raise RuntimeError("only shards with expire_after compact")
+        new_cap, cutoff = int(new_cap), int(cutoff)
+        fresh = lambda t: self._zeros_like_cap(t, new_cap)  # noqa: E731
+        table, flags, stamp, states = fresh(self.table), fresh(self.flags), fresh(self.stamp), \
+            [fresh(s) for s in self.states]
+        if self.gpu:
+            hkeys = torch.full((new_cap,), -1, dtype=torch.int64, device=self.device)
+            remap = _sp.compact_rows(self.hkeys, hkeys, self.table, table, self.flags, flags, self.stamp, stamp,
+                                     cutoff, self.counters, self.status, self.states, states)
+            self.hkeys = hkeys
+            self._snap = None  # a snapshot in flight counted the old map
+        else:
+            pairs = self.idmap.items()
+            pairs = pairs[torch.argsort(pairs[:, 1])]  # insertion order
+            keep = self.stamp[pairs[:, 1]] >= cutoff
+            src = pairs[keep, 1]
+            ns = int(src.numel())
+            if ns > new_cap:
+                raise ValueError(f"compact: {ns} surviving rows do not fit {new_cap}")
+            remap = torch.full((self.capacity,), -1, dtype=torch.int64)
+            remap[src] = torch.arange(ns)
+            for new, old in [(table, self.table), (flags, self.flags), (stamp, self.stamp)] + \
+                    list(zip(states, self.states)):
+                new[:ns] = old[src]
+            self.idmap = type(self.idmap)(new_cap)
+            self.idmap.restore(torch.stack([pairs[keep, 0], torch.arange(ns)], 1))
+            self.counters += torch.tensor([ns, pairs.shape[0] - ns])
+        self.table, self.flags, self.stamp, self.states = table, flags, stamp, states
+        self.capacity = new_cap
+        if self._pol is not None:
+            if live is not None:
+                self._pol.reset(new_cap, live)
+            else:  # (what ``admit`` did already if the decision was the policy's)
+                self._pol.in_flight, self._pol._mark, self._pol._resnap = False, 0, True
+            self._pol.cap = new_cap
+        self.stats["compactions"] = self.stats.get("compactions", 0) + 1
+        if self.on_grow is not None:
+            self.on_grow(remap)
+        return remap
 
     def _zeros_like_cap(self, t: torch.Tensor, cap: int) -> torch.Tensor:
         return torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
@@ -309,6 +461,11 @@ class RowShard:
             states = [self._zeros_like_cap(s, new_cap) for s in self.states]
             remap = _sp.rehash_rows(self.hkeys, hkeys, self.table, table, self.flags, flags, self.states, states)
             self.hkeys, self.table, self.flags, self.states = hkeys, table, flags, states
+            if self.stamp is not None:  # (growth of an expiring shard is a compaction; direct calls only)
+                stamp = self._zeros_like_cap(self.stamp, new_cap)
+                live = torch.nonzero(remap >= 0).reshape(-1)
+                stamp[remap[live]] = self.stamp[live]
+                self.stamp = stamp
             if self._pol is not None:
                 self._pol.cap = new_cap
         else:
@@ -319,6 +476,8 @@ class RowShard:
             self.idmap.restore(pairs)
             ext = lambda t: torch.cat([t, self._zeros_like_cap(t, new_cap - self.capacity)])  # noqa: E731
             self.table, self.flags, self.states = ext(self.table), ext(self.flags), [ext(s) for s in self.states]
+            if self.stamp is not None:
+                self.stamp = ext(self.stamp)
         self.capacity = new_cap
         if self.on_grow is not None:
             self.on_grow(remap)
@@ -357,6 +516,8 @@ class RowShard:
             d["hkeys"] = snap(self.hkeys)
         if self.idmap is not None:
             d["idmap"] = self.idmap.items()
+        if self.stamp is not None:
+            d["stamp"] = snap(self.stamp)
         return d
 
     def load_state_dict(self, d: dict) -> None:
@@ -370,8 +531,15 @@ class RowShard:
             self.hkeys.copy_(d["hkeys"])
         if self.idmap is not None and "idmap" in d:
             self.idmap.restore(d["idmap"])
+        if self.stamp is not None:  # (a shard without expiry ignores saved stamps)
+            self._cutoff = -(1 << 31)
+            if "stamp" in d:
+                self.stamp.copy_(d["stamp"])
+            else:  # written without expiry: every row counts as touched at the loaded round
+                self.stamp.fill_(int(d.get("round", 0)))
         if self._pol is not None and "hkeys" in d:  # exact count from the saved map, nothing in flight
-            self._pol = GrowthPolicy(self.capacity, live=int((d["hkeys"] != -1).sum()))
+            self._pol = GrowthPolicy(self.capacity, live=int((d["hkeys"] != -1).sum()),
+                                     expiring=bool(self.expire_after))
             self._snap = None
 
     def _adopt_capacity(self, d: dict) -> None:
@@ -382,6 +550,8 @@ class RowShard:
         self.table = self._zeros_like_cap(self.table, cap)
         self.flags = self._zeros_like_cap(self.flags, cap)
         self.states = [self._zeros_like_cap(s, cap) for s in self.states]
+        if self.stamp is not None:
+            self.stamp = self._zeros_like_cap(self.stamp, cap)
         if self.hkeys is not None:
             self.hkeys = torch.full((cap,), -1, dtype=torch.int64, device=self.device)
         if self.idmap is not None:
@@ -432,14 +602,28 @@ class ShardedSparseTable:
     ``rows``: rows per field (int, or one int per field).  ``fields`` > 1 makes lookups take
     ids of shape [..., fields] (one table for all fields of a layer).  ``grow`` (map mode): the
     shard enlarges itself when ``rows`` turns out too small (``stats["grows"]`` /
-    ``stats["capacity"]``); at W > 1 such tables use the collective exchange."""
+    ``stats["capacity"]``); at W > 1 such tables use the collective exchange.  ``expire_after`` = N
+    (needs ``grow``): a row no lookup touched for more than N rounds of ``self.round`` is dropped, and
+    its id, should it return, is a new row (``stats["compactions"]``, ``row_stats()["evicted"]``,
+    ``evict()``)."""
 
     def __init__(self, name: str, dim: int, rows: Union[int, Sequence[int]], transport: Optional[Transport] = None,
                  updater: Optional[Updater] = None, *, init: Tuple[float, float] = (0.0, 0.0),
                  id_mode: str = "direct", seed: int = 0, device=None, fields: int = 1, overlap: bool = False,
-                 average: bool = True, exchange: Optional[str] = None, grow: bool = False):
+                 average: bool = True, exchange: Optional[str] = None, grow: bool = False,
+                 expire_after: Optional[int] = None):
         if id_mode not in ("direct", "hash", "map"):
             raise ValueError(id_mode)
+        if expire_after is not None:
+            if not grow:
+                raise ValueError("expire_after needs grow=True (and so id_mode='map'): eviction is a rehash of a "
+                                 "growable shard's map")
+            if int(expire_after) < 1:
+                raise ValueError(f"expire_after must be >= 1 round (got {expire_after}): a row pulled in this "
+                                 "round still waits for its push")
+            if exchange == "plane":
+                raise ValueError("expire_after is not supported with exchange='plane': the row plane's accumulator "
+                                 "is sized by the shard; use the collective exchange")
         if grow and id_mode != "map":
             raise ValueError(f"grow=True needs id_mode='map' (got {id_mode!r}): other modes index rows directly")
         if grow and exchange == "plane":
@@ -467,7 +651,8 @@ class ShardedSparseTable:
         self.per_rank = (self.rows + self.world - 1) // self.world
         if id_mode == "map":
             cap = self.rows if self.world == 1 else int(self.per_rank * 1.25) + 64
-            self.shard = RowShard(dim, cap, "map", 0, seed, init, self.device, updater, grow=self.growable)
+            self.shard = RowShard(dim, cap, "map", 0, seed, init, self.device, updater, grow=self.growable,
+                                  expire_after=expire_after)
         else:
             self.shard = RowShard(dim, self.per_rank, "direct", self.rank * self.per_rank, seed, init, self.device,
                                   updater)
@@ -481,6 +666,9 @@ class ShardedSparseTable:
         self._push_done: Optional[torch.cuda.Event] = None
         self.stats = {"pulls": 0, "pushes": 0, "rows_pulled": 0, "rows_pushed": 0, "host_syncs": 0, "grows": 0,
                       "capacity": self.shard.capacity}
+        self.expire_after = int(expire_after) if expire_after is not None else 0
+        if self.expire_after:
+            self.stats["compactions"] = 0
         self.shard.stats = self.stats  # waits for a live-count snapshot count as host syncs
         self.shard.on_grow = self._on_grow
         self._pf: dict = {}  # ids signature -> (keys, route) of prefetched lookups
@@ -497,7 +685,8 @@ class ShardedSparseTable:
             if exchange not in (None, "auto", "plane", "collective"):
                 raise ValueError(exchange)
             if self.growable:  # every rank alike, so skipping the plane's probe is collective-safe
-                self.exchange_info["fallback"] = "growable table: the row plane does not migrate its accumulator"
+                what = "growable table with expiring rows" if self.expire_after else "growable table"
+                self.exchange_info["fallback"] = f"{what}: the row plane does not migrate its accumulator"
             elif _rp.plane_rows_wanted(self.t, self.device, exchange):
                 from .remote_probe import RemoteWriteUnavailable
 
@@ -580,8 +769,10 @@ class ShardedSparseTable:
     def _on_grow(self, remap: Optional[torch.Tensor]) -> None:
         """The shard grew (inside ``slots``, i.e. after ``_wait_push``: ordered behind every earlier
         update).  On the GPU slots moved: translate every owner-local slot still to be used --
-        the unpushed plans (in place: hook closures hold the plan) and the queued micro-batches."""
-        self.stats["grows"] += 1
+        the unpushed plans (in place: hook closures hold the plan) and the queued micro-batches.
+        A compaction comes here too (its capacity may not have risen, and it moves slots on the CPU
+        as well): the slot of an evicted row becomes -1 and its gradient is dropped."""
+        self.stats["grows"] += self.shard.capacity > self.stats["capacity"]
         self.stats["capacity"] = self.shard.capacity
         if remap is None:
             return
@@ -685,7 +876,7 @@ class ShardedSparseTable:
             self.t.all_to_all(rkeys, ukeys, recv, send)
         else:
             rkeys = ukeys
-        return rkeys, self.shard.slots(rkeys, insert=True)
+        return rkeys, self.shard.slots(rkeys, insert=True, now=self.round)
 
     def _rows_back(self, rows: torch.Tensor, nu: int, send: List[int], recv: List[int]) -> torch.Tensor:
         if self.world == 1:
@@ -971,7 +1162,26 @@ class ShardedSparseTable:
         d = dict(self.stats)
         if self.world == 1 and self.gpu:
             d["rows_pulled"] = int(self._rows_dev.item())
+        if self.expire_after:
+            d["evicted"] = int(self.shard.counters[1].item())
         return d
+
+    def evict(self, max_age: Optional[int] = None) -> int:
+        """Compact now (at an epoch end, say): drop this owner's rows that no lookup touched for more
+        than ``max_age`` rounds (default ``expire_after``) and re-size the shard for the survivors,
+        ``max(64, pow2(4 * survivors))`` slots -- it can shrink.  The survivors are counted exactly:
+        one host sync on the GPU (``stats["host_syncs"]``).  -> the number of survivors."""
+        if not self.expire_after:
+            raise ValueError(f"{self.name}: evict() needs a table built with expire_after")
+        max_age = self.expire_after if max_age is None else int(max_age)
+        if max_age < 1:
+            raise ValueError(f"{self.name}: max_age must be >= 1 round (got {max_age}): a row pulled in this round "
+                             "still waits for its push")
+        self._wait_push()
+        cutoff = self.round - max_age
+        n = self.shard.count_fresh(cutoff)
+        self.shard.compact(max(64, _pow2(4 * n)), cutoff, live=n)
+        return n
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self) -> dict:
@@ -994,9 +1204,9 @@ class SparseTable(ShardedSparseTable):
 
     def __init__(self, name: str, dim: int, rows: Union[int, Sequence[int]], updater: Optional[Updater] = None, *,
                  init: Tuple[float, float] = (0.0, 0.0), id_mode: str = "direct", seed: int = 0, device=None,
-                 fields: int = 1, overlap: bool = False, grow: bool = False):
+                 fields: int = 1, overlap: bool = False, grow: bool = False, expire_after: Optional[int] = None):
         super().__init__(name, dim, rows, None, updater, init=init, id_mode=id_mode, seed=seed, device=device,
-                         fields=fields, overlap=overlap, grow=grow)
+                         fields=fields, overlap=overlap, grow=grow, expire_after=expire_after)
 
 
 # ------------------------------------------------------------------------------ TCP rows
