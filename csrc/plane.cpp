@@ -30,11 +30,19 @@
 // Python callbacks that do the serve / pull / reduce work on shared-memory tensors.
 #include <torch/extension.h>
 
+#include <fcntl.h>
+#include <signal.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cstring>
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -102,6 +110,130 @@ struct ClipRound {
 double ms_between(Clock::time_point a, Clock::time_point b) {
   return std::chrono::duration<double, std::milli>(b - a).count();
 }
+
+// ------------------------------------------------------------------ inter-process events
+// An event another process on the node can make its streams wait on: the owner records it after
+// a kernel, a peer that opened the handle enqueues a wait -- the cross-process dependency lives
+// on the streams, the peer's host only waits until the record was ENQUEUED, never for it to run.
+// hipEventInterprocess is this protocol inside the runtime, but the runtime also pins (host-
+// registers) the event's shared-memory block, and where host registration is unavailable (a
+// virtual machine) hipIpcGetEventHandle fails with "invalid argument".  So the event is kept here,
+// without pinning: two counters in POSIX shared memory -- ``enq`` records enqueued, ``done``
+// records the owner's streams have reached -- moved by host functions on the streams
+// (hipLaunchHostFunc).  record = a host function that publishes the record's number; wait = a
+// host function that returns once ``done`` reached the ``enq`` read when the wait was enqueued.
+// The host functions touch host memory only; a wait whose owner process is gone gives up and
+// poisons the event (the next call on it raises) instead of stalling its stream for ever.
+class ShmEvent {
+ public:
+  ShmEvent() : own_(true) {
+    static std::atomic<uint64_t> seq{0};
+    name_ = "/psamd_ev_" + std::to_string(getpid()) + "_" + std::to_string(seq.fetch_add(1)) + "_" +
+            std::to_string(Clock::now().time_since_epoch().count() % 1000000007ll);
+    const int fd = shm_open(name_.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
+    TORCH_CHECK(fd >= 0, "shm_open(", name_, "): ", std::strerror(errno));
+    const bool sized = ftruncate(fd, sizeof(Block)) == 0;
+    void* p = sized ? mmap(nullptr, sizeof(Block), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : MAP_FAILED;
+    ::close(fd);
+    if (p == MAP_FAILED) shm_unlink(name_.c_str());
+    TORCH_CHECK(p != MAP_FAILED, "mapping ", name_, ": ", std::strerror(errno));
+    m_ = std::make_shared<Map>(static_cast<Block*>(p));
+    psasync::st(&m_->b->pid, static_cast<int64_t>(getpid()));  // (a fresh segment is zero-filled)
+  }
+  explicit ShmEvent(const std::string& handle) : name_(handle), own_(false) {
+    TORCH_CHECK(handle.rfind("/psamd_ev_", 0) == 0 && handle.size() < 64, "bad inter-process event handle");
+    const int fd = shm_open(name_.c_str(), O_RDWR, 0);
+    TORCH_CHECK(fd >= 0, "shm_open(", name_, "): ", std::strerror(errno));
+    void* p = mmap(nullptr, sizeof(Block), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    ::close(fd);
+    TORCH_CHECK(p != MAP_FAILED, "mapping ", name_, ": ", std::strerror(errno));
+    m_ = std::make_shared<Map>(static_cast<Block*>(p));
+  }
+  ShmEvent(const ShmEvent&) = delete;
+  ShmEvent& operator=(const ShmEvent&) = delete;
+  // (host functions still queued keep the mapping alive)
+  ~ShmEvent() {
+    if (own_) shm_unlink(name_.c_str());
+  }
+  const std::string& handle() const {
+    TORCH_CHECK(own_, "only the creating process exports the handle");
+    return name_;
+  }
+  void record(hipStream_t stream) {
+    TORCH_CHECK(own_, "only the creating process records the event");
+    const int64_t v = psasync::ld(&m_->b->enq) + 1;
+    enqueue(stream, &ShmEvent::reached, v, "hipLaunchHostFunc(record)");
+    psasync::st(&m_->b->enq, v);  // (the caller tells the peers afterwards that it is enqueued)
+  }
+  void wait(hipStream_t stream) {
+    check();
+    const int64_t v = psasync::ld(&m_->b->enq);
+    if (psasync::ld(&m_->b->done) < v) enqueue(stream, &ShmEvent::await, v, "hipLaunchHostFunc(wait)");
+  }
+  bool query() const {
+    check();
+    return psasync::ld(&m_->b->done) >= psasync::ld(&m_->b->enq);
+  }
+  void synchronize() const {
+    check();
+    until(*m_, psasync::ld(&m_->b->enq));
+    check();
+  }
+  int64_t ptr() const { return reinterpret_cast<int64_t>(m_->b); }
+
+ private:
+  struct Block {
+    int64_t enq, done, pid;
+  };
+  struct Map {
+    explicit Map(Block* blk) : b(blk) {}
+    ~Map() { munmap(b, sizeof(Block)); }
+    Block* b;
+    std::atomic<bool> orphan{false};
+  };
+  struct Hook {
+    std::shared_ptr<Map> m;
+    int64_t v;
+  };
+  void check() const { TORCH_CHECK(!m_->orphan.load(), "the owner of inter-process event ", name_, " exited"); }
+  void enqueue(hipStream_t stream, void (*fn)(void*), int64_t v, const char* what) {
+    Hook* h = new Hook{m_, v};
+    const hipError_t e = hipLaunchHostFunc(stream, fn, h);
+    if (e != hipSuccess) delete h;
+    hip_ok(e, what);
+  }
+  // records on several streams may be reached out of order: done only grows
+  static void reached(void* p) {
+    Hook* h = static_cast<Hook*>(p);
+    int64_t cur = psasync::ld(&h->m->b->done);
+    while (cur < h->v &&
+           !__atomic_compare_exchange_n(&h->m->b->done, &cur, h->v, false, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE)) {
+    }
+    delete h;
+  }
+  static void await(void* p) {
+    Hook* h = static_cast<Hook*>(p);
+    until(*h->m, h->v);
+    delete h;
+  }
+  static void until(Map& m, int64_t v) {
+    psasync::Backoff bo;
+    auto looked = Clock::now();
+    while (psasync::ld(&m.b->done) < v) {
+      bo();
+      if (Clock::now() - looked < std::chrono::milliseconds(50)) continue;
+      looked = Clock::now();
+      if (kill(static_cast<pid_t>(psasync::ld(&m.b->pid)), 0) != 0 && errno == ESRCH &&
+          psasync::ld(&m.b->done) < v) {
+        m.orphan.store(true);
+        return;
+      }
+    }
+  }
+  std::string name_;
+  bool own_;
+  std::shared_ptr<Map> m_;
+};
 
 class PlaneEngine {
  public:
@@ -292,12 +424,8 @@ class PlaneEngine {
     ring_ = static_cast<int>(ring);
     std::vector<py::bytes> out;
     for (int i = 0; i < NB_ * ring_; ++i) {
-      hipEvent_t ev;
-      hip_ok(hipEventCreateWithFlags(&ev, hipEventInterprocess | hipEventDisableTiming), "hipEventCreate(ipc)");
-      own_ev_.push_back(ev);
-      hipIpcEventHandle_t h;
-      hip_ok(hipIpcGetEventHandle(&h, ev), "hipIpcGetEventHandle");
-      out.emplace_back(reinterpret_cast<const char*>(&h), sizeof(h));
+      own_ev_.push_back(std::make_unique<ShmEvent>());
+      out.emplace_back(own_ev_.back()->handle());
     }
     return out;
   }
@@ -305,19 +433,12 @@ class PlaneEngine {
   void enable_ipc_events(std::vector<std::vector<py::bytes>> handles) {
     TORCH_CHECK(static_cast<int>(handles.size()) == W_ && ring_ > 0, "one handle list per rank");
     hip_ok(hipSetDevice(dev_), "hipSetDevice");
-    peer_ev_.assign(static_cast<size_t>(W_), {});
+    peer_ev_.clear();
+    peer_ev_.resize(static_cast<size_t>(W_));
     for (int r = 0; r < W_; ++r) {
       if (r == me_) continue;
       TORCH_CHECK(static_cast<int>(handles[r].size()) == NB_ * ring_, "ring size mismatch");
-      for (auto& hb : handles[r]) {
-        std::string st = hb;
-        TORCH_CHECK(st.size() == sizeof(hipIpcEventHandle_t), "bad IPC event handle");
-        hipIpcEventHandle_t h;
-        std::memcpy(&h, st.data(), sizeof(h));
-        hipEvent_t ev;
-        hip_ok(hipIpcOpenEventHandle(&ev, h), "hipIpcOpenEventHandle");
-        peer_ev_[static_cast<size_t>(r)].push_back(ev);
-      }
+      for (auto& hb : handles[r]) peer_ev_[static_cast<size_t>(r)].push_back(std::make_unique<ShmEvent>(std::string(hb)));
     }
     std::lock_guard<std::mutex> g(mu_);
     ipc_ = true;
@@ -403,10 +524,7 @@ class PlaneEngine {
       hipStreamDestroy(serve_s_);
       hipStreamDestroy(pull_s_);
     }
-    for (auto& v : peer_ev_)
-      for (auto ev : v) hipEventDestroy(ev);
     peer_ev_.clear();
-    for (auto ev : own_ev_) hipEventDestroy(ev);
     own_ev_.clear();
   }
 
@@ -578,8 +696,7 @@ class PlaneEngine {
             const size_t k = static_cast<size_t>(j.b * ring_ + j.round % ring_);
             hip_ok(hipStreamWaitEvent(pull_s_, j.s1, 0), "hipStreamWaitEvent(own serve)");
             for (int o = 0; o < W_; ++o)
-              if (o != me_) hip_ok(hipStreamWaitEvent(pull_s_, peer_ev_[static_cast<size_t>(o)][k], 0),
-                                   "hipStreamWaitEvent(peer serve)");
+              if (o != me_) peer_ev_[static_cast<size_t>(o)][k]->wait(pull_s_);
           }
           j.p0 = record(pull_s_, true);
           launch_pull(bk, j.wslot, pull_s_);
@@ -606,7 +723,7 @@ class PlaneEngine {
   void publish_enqueued(Job& j) {
     if (!ipc_ || !gpu_) return;
     const size_t k = static_cast<size_t>(j.b * ring_ + j.round % ring_);
-    hip_ok(hipEventRecord(own_ev_[k], serve_s_), "hipEventRecord(ipc)");
+    own_ev_[k]->record(serve_s_);
     store_max(ctl_.served(me_, j.b), j.round + 1);
     j.t_served = Clock::now();
     j.stage = SERVED;
@@ -834,8 +951,8 @@ class PlaneEngine {
   // another rank's serve kernel to finish.  Ring of R events per bucket, slot = round % R.
   bool ipc_ = false;
   int ring_ = 0;
-  std::vector<hipEvent_t> own_ev_;
-  std::vector<std::vector<hipEvent_t>> peer_ev_;
+  std::vector<std::unique_ptr<ShmEvent>> own_ev_;
+  std::vector<std::vector<std::unique_ptr<ShmEvent>>> peer_ev_;
 
   // engine-thread state
   std::thread th_;
@@ -1042,51 +1159,23 @@ class VmmArena {
 };
 
 // ------------------------------------------------------------------ IPC events
-// An event another process on the node can make its streams wait on (hipEventInterprocess):
-// the owner records it after a kernel, a peer that opened the handle enqueues
-// hipStreamWaitEvent -- the cross-process dependency lives on the device queues, the peer's
-// host only waits until the record was ENQUEUED (a flag in shared memory), never for it to run.
+// ShmEvent for Python (the row plane's stages, ps_amd/parallel/row_plane.py): streams come as
+// integers, the handle as bytes.
 class IpcEvent {
  public:
-  explicit IpcEvent(int64_t device) : dev_(static_cast<int>(device)) {
-    hip_ok(hipSetDevice(dev_), "hipSetDevice");
-    hip_ok(hipEventCreateWithFlags(&ev_, hipEventInterprocess | hipEventDisableTiming), "hipEventCreate(ipc)");
-    own_ = true;
+  explicit IpcEvent(int64_t device) { hip_ok(hipSetDevice(static_cast<int>(device)), "hipSetDevice"); }
+  IpcEvent(py::bytes hb, int64_t device) : ev_(std::string(hb)) {
+    hip_ok(hipSetDevice(static_cast<int>(device)), "hipSetDevice");
   }
-  IpcEvent(py::bytes hb, int64_t device) : dev_(static_cast<int>(device)) {
-    std::string s = hb;
-    TORCH_CHECK(s.size() == sizeof(hipIpcEventHandle_t), "bad IPC event handle");
-    hipIpcEventHandle_t h;
-    std::memcpy(&h, s.data(), sizeof(h));
-    hip_ok(hipSetDevice(dev_), "hipSetDevice");
-    hip_ok(hipIpcOpenEventHandle(&ev_, h), "hipIpcOpenEventHandle");
-  }
-  ~IpcEvent() {
-    if (ev_ != nullptr) hipEventDestroy(ev_);
-  }
-  py::bytes handle() const {
-    TORCH_CHECK(own_, "only the creating process exports the handle");
-    hipIpcEventHandle_t h;
-    hip_ok(hipIpcGetEventHandle(&h, ev_), "hipIpcGetEventHandle");
-    return py::bytes(reinterpret_cast<const char*>(&h), sizeof(h));
-  }
-  void record(int64_t stream) { hip_ok(hipEventRecord(ev_, reinterpret_cast<hipStream_t>(stream)), "hipEventRecord"); }
-  void wait(int64_t stream) {
-    hip_ok(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), ev_, 0), "hipStreamWaitEvent");
-  }
-  bool query() const {
-    const hipError_t e = hipEventQuery(ev_);
-    if (e == hipSuccess) return true;
-    TORCH_CHECK(e == hipErrorNotReady, "hipEventQuery: ", hipGetErrorString(e));
-    return false;
-  }
-  void synchronize() const { hip_ok(hipEventSynchronize(ev_), "hipEventSynchronize"); }
-  int64_t ptr() const { return reinterpret_cast<int64_t>(ev_); }
+  py::bytes handle() const { return py::bytes(ev_.handle()); }
+  void record(int64_t stream) { ev_.record(reinterpret_cast<hipStream_t>(stream)); }
+  void wait(int64_t stream) { ev_.wait(reinterpret_cast<hipStream_t>(stream)); }
+  bool query() const { return ev_.query(); }
+  void synchronize() const { ev_.synchronize(); }
+  int64_t ptr() const { return ev_.ptr(); }
 
  private:
-  int dev_;
-  hipEvent_t ev_ = nullptr;
-  bool own_ = false;
+  ShmEvent ev_;
 };
 
 }  // namespace

@@ -7,7 +7,9 @@ above 2 GiB (1.99 GiB opens at once, 2.01 GiB never returns; profiles/r6_plane_i
 Llama-3-8B plane arena is ~34 GB.  The descriptors reach the peers over an abstract Unix socket
 (SCM_RIGHTS): the exporter serves its fds from a thread, a peer connects, receives them, imports
 every chunk and maps them back to back, so both sides see one contiguous arena and the plane
-engine's base + offset addressing does not change.
+engine's base + offset addressing does not change.  A machine whose driver refuses the import of
+another process's chunk (seen on virtual machines: hipMemImportFromShareableHandle returns "invalid
+argument") cannot share arenas above 1 GiB; ``open`` raises there.
 """
 from __future__ import annotations
 

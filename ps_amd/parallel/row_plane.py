@@ -28,7 +28,7 @@ Cross-rank ordering: a POSIX shared-memory control block holds one epoch word pe
 rank); a rank bumps its word right after ENQUEUEING the stage, and the consumer of a stage waits
 (on the host) only until every peer's word reached the epoch -- i.e. until the peers ENQUEUED
 their part -- then makes its stream wait on the peers' inter-process events (GPU processes:
-hipEventInterprocess handles, csrc/plane.cpp IpcEvent; GPU thread-ranks: shared events; CPU
+shared-memory events, csrc/plane.cpp ShmEvent / IpcEvent; GPU thread-ranks: shared events; CPU
 ranks: every stage is synchronous).  No device->host copy of a count or size anywhere.  Every
 reuse of a buffer is ordered by a wait on the stage that last read it (pull t+1 overwrites skeys
 after its stream waited for the owners' rows of pull t; push t+1 overwrites grads after waiting

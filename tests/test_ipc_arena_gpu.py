@@ -40,8 +40,42 @@ def _body(tp, gb, vmm):
     return a.vmm, offs, out
 
 
+def _import_probe(tp):
+    """One small VMM chunk each: can this process import the other's dma-buf descriptor?"""
+    from ps_amd.parallel.ipc_arena import IpcArena
+
+    torch.cuda.set_device(0)
+    a = IpcArena(1 << 21, 0, vmm=True)
+    hs = tp.all_gather_object(a.handle())
+    err = None
+    try:
+        a.open(hs[1 - tp.rank], 0)
+    except RuntimeError as e:
+        err = str(e)
+    tp.barrier()
+    a.close()
+    return err
+
+
+_NO_IMPORT = []
+
+
+def _skip_without_dmabuf_import():
+    """Some machines (virtual ones) refuse the import of a chunk another process exported
+    (hipMemImportFromShareableHandle: invalid argument; importing one's own chunk works): VMM
+    arenas cannot be shared there.  Any other failure is left to the test."""
+    if not _NO_IMPORT:
+        errs = dist_util.run(_import_probe, 2)
+        _NO_IMPORT.append(all(e is not None and e.startswith("hipMemImportFromShareableHandle: invalid argument")
+                              for e in errs))
+    if _NO_IMPORT[0]:
+        pytest.skip("hipMemImportFromShareableHandle rejects another process's dma-buf descriptor here")
+
+
 @pytest.mark.parametrize("gb,vmm", [(0.25, False), (0.25, True), (3.0, None)])
 def test_ipc_arena_peer_reads(gb, vmm):
+    if vmm or (vmm is None and gb > 1.0):
+        _skip_without_dmabuf_import()
     res = dist_util.run(_body, 2, (gb, vmm))
     for rank, (is_vmm, offs, out) in enumerate(res):
         assert is_vmm == (vmm if vmm is not None else gb > 1.0)
