@@ -1158,12 +1158,13 @@ Tensor attn_dropout_mask(Tensor like, int64_t bh, int64_t S, double p, int64_t s
   return m;
 }
 
-// Causal GQA flash attention: q [B, H, S, 128], k / v [B, KV, S, 128] -> [out [B, S, H * 128], lse [B, H, S]]
+// Causal GQA flash attention: q [B, H, S, D], k / v [B, KV, S, D], D = 64 or 128 -> [out [B, S, H * D], lse [B, H, S]]
 static void check_fa(const Tensor& q, const Tensor& k, const Tensor& v) {
   for (const Tensor* t : {&q, &k, &v}) {
     check_gpu(*t, "q/k/v");
-    TORCH_CHECK(t->scalar_type() == torch::kBFloat16 && t->is_contiguous() && t->dim() == 4 && t->size(3) == 128,
-                "q / k / v: contiguous bf16 [B, heads, S, 128]");
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16 && t->is_contiguous() && t->dim() == 4 &&
+                    (t->size(3) == 64 || t->size(3) == 128) && t->size(3) == q.size(3),
+                "q / k / v: contiguous bf16 [B, heads, S, D], D = 64 or 128, the same for all three");
   }
   TORCH_CHECK(k.sizes() == v.sizes() && q.size(0) == k.size(0) && q.size(2) == k.size(2), "k like v, q matches");
   TORCH_CHECK(q.size(1) % k.size(1) == 0, "q heads a multiple of kv heads");
@@ -1214,27 +1215,27 @@ static const int32_t* fa_bound(const c10::optional<Tensor>& bound, const Tensor&
 
 std::vector<Tensor> fa_fwd(Tensor q, Tensor k, Tensor v, c10::optional<Tensor> doc_start) {
   check_fa(q, k, v);
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1), D = q.size(3);
   const int32_t* ds = fa_bound(doc_start, q, "doc_start");
   const c10::DeviceGuard guard(q.device());
-  auto out = torch::empty({B, S, H * 128}, q.options());
+  auto out = torch::empty({B, S, H * D}, q.options());
   auto lse = torch::empty({B, H, S}, q.options().dtype(torch::kFloat32));
   psamd::launch_fa_fwd(u16(q), u16(k), u16(v), u16m(out), lse.data_ptr<float>(), static_cast<int>(B),
-                       static_cast<int>(S), static_cast<int>(H), static_cast<int>(KV), 1.f / std::sqrt(128.f),
-                       cur_stream(q), ds);
+                       static_cast<int>(S), static_cast<int>(H), static_cast<int>(KV), static_cast<int>(D),
+                       1.f / std::sqrt(static_cast<float>(D)), cur_stream(q), ds);
   return {out, lse};
 }
 
 std::vector<Tensor> fa_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor lse,
                            c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end) {
   check_fa(q, k, v);
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1), D = q.size(3);
   TORCH_CHECK(doc_start.has_value() == doc_end.has_value(), "fa_bwd: doc_start and doc_end, or neither");
   const int32_t* ds = fa_bound(doc_start, q, "doc_start");
   const int32_t* de = fa_bound(doc_end, q, "doc_end");
   check_rows(out, "out");
   check_rows(dout, "dout");
-  TORCH_CHECK(out.numel() == B * S * H * 128 && dout.numel() == out.numel(), "out / dout [B, S, H * 128]");
+  TORCH_CHECK(out.numel() == B * S * H * D && dout.numel() == out.numel(), "out / dout [B, S, H * D], D = 64 or 128");
   check_gpu(lse, "lse");
   TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.numel() == B * H * S, "lse fp32 [B, H, S]");
   const c10::DeviceGuard guard(q.device());
@@ -1244,7 +1245,7 @@ std::vector<Tensor> fa_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout
   psamd::launch_fa_bwd(u16(q), u16(k), u16(v), u16(out), u16(dout), lse.data_ptr<float>(), dsum.data_ptr<float>(),
                        u16m(dq), u16m(dk), u16m(dv),
                        static_cast<int>(B), static_cast<int>(S), static_cast<int>(H), static_cast<int>(KV),
-                       1.f / std::sqrt(128.f), cur_stream(q), ds, de);
+                       static_cast<int>(D), 1.f / std::sqrt(static_cast<float>(D)), cur_stream(q), ds, de);
   return {dq, dk, dv};
 }
 

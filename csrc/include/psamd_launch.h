@@ -612,8 +612,8 @@ void launch_attn_long_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B,
 void launch_attn_long_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
                           uint16_t* dqkv, int B, int S, int H, float scale, float p, uint64_t seed, hipStream_t s,
                           const int32_t* klen = nullptr, const int32_t* cu = nullptr, int T = 0);
-// Causal GQA flash attention (flash_attn.hip): q [B, H, S, 128], k / v [B, KV, S, 128] bf16,
-// out [B, S, H * 128], lse / dsum [B, H, S] fp32; S % 128 == 0
+// Causal GQA flash attention (flash_attn.hip, flash_attn_d64.hip): head dim D = 64 or 128;
+// q [B, H, S, D], k / v [B, KV, S, D] bf16, out [B, S, H * D], lse / dsum [B, H, S] fp32; S % 128 == 0
 // Fused softmax cross-entropy over bf16 logits [R, V] (xent.hip): forward lse / per-row loss,
 // backward dx = (softmax - onehot) * go / count (go, count: device scalars); ignored rows -> 0
 void launch_xent_fwd(const uint16_t* x, const int64_t* lab, int64_t R, int V, int64_t ignore, float* lse, float* loss,
@@ -621,13 +621,14 @@ void launch_xent_fwd(const uint16_t* x, const int64_t* lab, int64_t R, int V, in
 void launch_xent_bwd(const uint16_t* x, const int64_t* lab, const float* lse, int64_t R, int V, int64_t ignore,
                      const float* go, const float* count, uint16_t* dx, hipStream_t s);
 void launch_fa_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, float* lse, int B, int S,
-                   int H, int KV, float scale, hipStream_t s, const int* doc_start = nullptr);
+                   int H, int KV, int D, float scale, hipStream_t s, const int* doc_start = nullptr);
 // packed documents (flash_attn.hip): doc_start / doc_end (nullable, device, int32 [B, S], non-decreasing
 // along S): query i of row b sees keys doc_start[b, i] <= j <= i, key j is seen by queries
 // j <= i < doc_end[b, j]; the kernels clamp every bound into the row.  The backward takes both or neither
 void launch_fa_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
                    const float* lse, float* dsum, uint16_t* dq, uint16_t* dk, uint16_t* dv, int B, int S, int H,
-                   int KV, float scale, hipStream_t s, const int* doc_start = nullptr, const int* doc_end = nullptr);
+                   int KV, int D, float scale, hipStream_t s, const int* doc_start = nullptr,
+                   const int* doc_end = nullptr);
 void launch_conv_wgrad(const ConvWgradArgs& a, hipStream_t s);
 // BN helpers for the fused bottleneck (bn_act.hip): y = act(x*scale + shift [+ res [* rscale + rshift]])
 // mbits (nullable): also write the ReLU mask of y, 1 bit per element

@@ -92,6 +92,16 @@ __device__ __forceinline__ void dma_tile128(uint16_t* T, const uint16_t* src, in
   }
 }
 
+// The same for a [rows][64] bf16 tile (rows % 8 == 0): 128-B rows, so one wave instruction moves 8 rows.
+__device__ __forceinline__ void dma_tile64(uint16_t* T, const uint16_t* src, int64_t rs, int rows, int wave, int nw,
+                                           int lane) {
+  for (int i = wave; i < rows / 8; i += nw) {
+    const int lc = i * 64 + lane, r = lc >> 3, pc = lc & 7;
+    const uint16_t* g = src + r * rs + ((pc ^ sw<64>(r)) << 3);
+    __builtin_amdgcn_global_load_lds((gptr_t*)g, (lptr_t*)(T + i * 512), 16, 0, 0);
+  }
+}
+
 __device__ __forceinline__ uint32_t pack2(float a, float b) { return pk_bf16(a, b); }
 
 // v_permlane32_swap(x, y): x's upper 32 lanes <-> y's lower 32 lanes (a VALU op: no LDS queue,

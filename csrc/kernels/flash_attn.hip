@@ -1,7 +1,9 @@
 // Causal grouped-query flash attention (Llama-3: head dim 128, S a multiple of 128), forward and
 // backward on v_mfma_f32_32x32x16_bf16 -- the default attention of the Llama family; on the
 // Llama-3-8B bench shape it runs ahead of SDPA's library kernels forward and backward
-// (profiles/r3_flash_v3_probe.jsonl).
+// (profiles/r3_flash_v3_probe.jsonl).  Head dim 64 (Llama-3.2-1B) has kernels of its own in
+// flash_attn_d64.hip; launch_fa_fwd / launch_fa_bwd below dispatch on the head dim, and what both files
+// share is in psamd_flash.h.  Other head dims and S % 128 != 0 are not covered.
 //
 // Forward / dQ (grid: query blocks of 256 (8 waves x 32 queries) x heads x batch): the block's
 // keys stream through a double-buffered LDS image 64 at a time, prefetched into registers two
@@ -22,18 +24,17 @@
 // 15 VALU instructions per MFMA), so it is kept lean: bare v_exp_f32 (fast_exp2), one packed
 // bf16 convert per pair (pk_bf16), and the causal mask only on diagonal tiles / slices
 // (profiles/r5_flash_valu_trim.txt: bwd -18 %, fwd -17 %).
-#include "psamd_launch.h"
-#include "psamd_mfma.h"
+#include "psamd_flash.h"
 
 namespace psamd {
 namespace {
 
 using namespace mfma;
+using namespace flash;  // kLog2e, kRescale, xcd_unit, clampi, lgkm_wait, lds_f4, tie4
 
 constexpr int kD = 128;   // head dim
 constexpr int kBQ = 128;  // queries per block (4 waves x 32)
 constexpr int kBK = 64;   // keys per forward / dQ iteration
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kNeg = -3.0e38f;
 
 // [rows][128] swizzled tile from rows of stride rs elements
@@ -57,22 +58,6 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[4], uint16_t* row, f
 }
 
 // ------------------------------------------------------------------------------ forward
-// XCD-aware 1-D block order.  The hardware deals consecutive block ids round-robin over the 8
-// XCDs, each with its own L2; a "unit" is every block that reads one (batch, KV head)'s K / V
-// (forward, dQ) or Q / dO (dK / dV), so each XCD is given whole units -- block L runs on XCD
-// L mod 8 and takes the (L / 8) mod per -th item of unit (L mod 8) + 8 ((L / 8) / per).  Needs
-// units % 8 == 0 (else plain order).  Items run heaviest first within a unit.
-__device__ __forceinline__ void xcd_unit(int L, int per, int units, int& unit, int& r) {
-  if ((units & 7) == 0) {
-    const int x = L & 7, j = L >> 3;
-    unit = x + 8 * (j / per);
-    r = j % per;
-  } else {
-    unit = L / per;
-    r = L % per;
-  }
-}
-
 // S^T for one 64-key block from the LDS tile (asm reads: a DMA into the other buffer is in flight)
 __device__ __forceinline__ void st_block(const uint16_t* Ks, const bf16x8_t (&qf)[8], int c, int hl, f32x16 (&st)[2]) {
   zero(st[0]);
@@ -121,15 +106,13 @@ __device__ __forceinline__ void pv_block(const uint16_t* T, const f32x16 (&pt)[2
 // fragment reads.  The online softmax keeps a deferred reference max (rescale only when the
 // running max grows by more than 2^8 in exp2 units): O and l are exact against that reference,
 // P stays <= 256.  Query blocks run latest-first: under the causal mask the last blocks carry
-// the most keys, and starting them first keeps the tail short.
-constexpr float kRescale = 8.f;
-
+// the most keys, and starting them first keeps the tail short.  (kRescale: psamd_flash.h.)
+//
 // DOCS (packed documents): query i of row b sees keys doc_start[b, i] <= j <= i.  The bound is
 // non-decreasing along the row, so the block's key loop starts at the tile that holds the bound of
 // its first query, a wave skips tiles that end before the bound of its first query, and only tiles
 // that begin before the bound of its last query take the lower-bound mask (by select).  Every bound
 // is clamped to [0, query], so malformed bounds cannot move an address out of the tensors.
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
 
 // the bounds a forward / dQ lane works with, from its row ds of doc_start: lo of its own query qi (one
 // VGPR); uniform (SGPRs): kb0, the first key tile of the block whose first query is qblk, and wlo0 /
@@ -411,18 +394,6 @@ __global__ __launch_bounds__(NW * 64) void fa_bwd_dq_kernel(const uint16_t* __re
 // all transposed dO / Q fragments behind the dP chain and under the softmax VALU work.
 constexpr int kBQS = 64;  // queries per dK / dV stage
 
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ f32x4 lds_f4(const float* p) {
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(reinterpret_cast<const uint16_t*>(p))) : "memory");
-  return v;
-}
-__device__ __forceinline__ void tie4(f32x4& v) { asm volatile("" : "+v"(v)); }
-
-//
 // DOCS: key j is seen by queries j <= i < doc_end[b, j] (non-decreasing along the row).  The block's
 // query stages end with the document of its last key, a wave skips the 32-query slices at or beyond
 // the bound of its last key, and slices that reach the bound of its first key take the upper-bound
@@ -596,9 +567,11 @@ __global__ __launch_bounds__(256) void fa_bwd_dkdv_kernel(const uint16_t* __rest
 }  // namespace
 
 // doc_start / doc_end (device int32 [B, S], or nullptr): the document instantiations; nullptr selects
-// the plain ones, which compile to what they were without the DOCS parameter
+// the plain ones, which compile to what they were without the DOCS parameter.  D (64 or 128, checked by
+// the caller): 64 goes to flash_attn_d64.hip, 128 runs the kernels of this file as before
 void launch_fa_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, float* lse, int B, int S,
-                   int H, int KV, float scale, hipStream_t s, const int* doc_start) {
+                   int H, int KV, int D, float scale, hipStream_t s, const int* doc_start) {
+  if (D == 64) return launch_fa64_fwd(q, k, v, out, lse, B, S, H, KV, scale, s, doc_start);
   const bool w8 = S % 256 == 0;
   auto* kern = w8 ? (doc_start ? fa_fwd_kernel<8, true> : fa_fwd_kernel<8, false>)
                   : (doc_start ? fa_fwd_kernel<4, true> : fa_fwd_kernel<4, false>);
@@ -608,7 +581,8 @@ void launch_fa_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint
 
 void launch_fa_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
                    const float* lse, float* dsum, uint16_t* dq, uint16_t* dk, uint16_t* dv, int B, int S, int H,
-                   int KV, float scale, hipStream_t s, const int* doc_start, const int* doc_end) {
+                   int KV, int D, float scale, hipStream_t s, const int* doc_start, const int* doc_end) {
+  if (D == 64) return launch_fa64_bwd(q, k, v, out, dout, lse, dsum, dq, dk, dv, B, S, H, KV, scale, s, doc_start, doc_end);
   const bool w8 = S % 256 == 0, docs = doc_start != nullptr;
   auto* kq = w8 ? (docs ? fa_bwd_dq_kernel<8, true> : fa_bwd_dq_kernel<8, false>)
                 : (docs ? fa_bwd_dq_kernel<4, true> : fa_bwd_dq_kernel<4, false>);

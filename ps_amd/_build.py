@@ -26,6 +26,7 @@ PKG = ROOT / "ps_amd"
 BUILD = ROOT / "build"
 ARCH = os.environ.get("PS_AMD_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+HIP_SCALAR_F32 = {"flash_attn_d64"}  # kernel sources compiled with packed fp32 VALU operations off
 
 
 def _torch_paths():
@@ -76,6 +77,11 @@ def _write_ninja() -> Path:
         "  depfile = $out.d",
         "  deps = gcc",
         "  description = HIPCC $in",
+        "rule hip_scalar_f32",  # HIP_SCALAR_F32 sources: packed fp32 VALU operations (v_pk_*_f32) off
+        "  command = $hipcc $hipflags -Xclang -target-feature -Xclang -packed-fp32-ops -c $in -o $out -MD -MF $out.d",
+        "  depfile = $out.d",
+        "  deps = gcc",
+        "  description = HIPCC $in",
         "rule bind",
         "  command = $cxx $bindflags -c $in -o $out -MD -MF $out.d",
         "  depfile = $out.d",
@@ -97,7 +103,7 @@ def _write_ninja() -> Path:
     for s in hip_srcs:
         o = BUILD / (s.stem + ".hip.o")
         objs.append(o)
-        lines.append(f"build {o}: hip {s}")
+        lines.append(f"build {o}: {'hip_scalar_f32' if s.stem in HIP_SCALAR_F32 else 'hip'} {s}")
     for src in sorted((ROOT / "csrc").glob("*.cpp")):  # bindings.cpp + host-side GPU runtime (async PS)
         bo = BUILD / (src.stem + ".o")
         lines.append(f"build {bo}: bind {src}")

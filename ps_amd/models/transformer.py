@@ -243,6 +243,12 @@ class LlamaConfig:
         return LlamaConfig()
 
     @staticmethod
+    def llama32_1b() -> "LlamaConfig":
+        """The shapes of Llama-3.2-1B: head dim 64, 4 query heads per KV head.  Shapes only: the released
+        checkpoint's tied input / output embeddings and its RoPE frequency scaling are not modelled."""
+        return LlamaConfig(vocab=128256, hidden=2048, layers=16, heads=32, kv_heads=8, ffn=8192, rope_theta=500000.0)
+
+    @staticmethod
     def tiny() -> "LlamaConfig":
         return LlamaConfig(vocab=512, hidden=64, layers=2, heads=4, kv_heads=2, ffn=128, max_seq=128)
 

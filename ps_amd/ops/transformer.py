@@ -377,10 +377,12 @@ def attention_qkv(qkv: torch.Tensor, heads: int, p: float = 0.0, mask: Optional[
 
 # ------------------------------------------------------------------------------ causal GQA flash attention
 def flash_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
-    """The in-house causal GQA flash kernels are the default for head dim 128 (PS_AMD_DISABLE=flash_attn
-    falls back to SDPA): on the Llama-3-8B shape they beat SDPA's library kernels forward and
-    backward (profiles/r3_flash_v3_probe.jsonl) and end to end (profiles/r3_llama_flash_vs_sdpa.jsonl)."""
-    return (_hip(q, k, v) and q.dim() == 4 and q.shape[3] == 128 and k.shape == v.shape and q.shape[2] % 128 == 0
+    """The in-house causal GQA flash kernels are the default for head dim 64 or 128 (PS_AMD_DISABLE=flash_attn
+    falls back to SDPA; a head dim other than 64 or 128 takes SDPA): on the Llama-3-8B shape they beat
+    SDPA's library kernels forward and backward (profiles/r3_flash_v3_probe.jsonl) and end to end
+    (profiles/r3_llama_flash_vs_sdpa.jsonl); head dim 64, the Llama-3.2-1B shape: profiles/flash_d64_probe.txt."""
+    return (_hip(q, k, v) and q.dim() == 4 and q.shape[3] in (64, 128) and k.shape[3] == q.shape[3]
+            and k.shape == v.shape and q.shape[2] % 128 == 0
             and q.shape[1] % k.shape[1] == 0 and knobs.enabled("flash_attn"))
 
 
@@ -446,7 +448,7 @@ def attention_causal_gqa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, doc_
     ``doc_bounds`` = (doc_start, doc_end) (``doc_bounds(doc_ids)``; integer [B, S]) describes packed
     rows: query i of row b sees keys ``doc_start[b, i] <= j <= i`` only, its own document.  In the
     flash domain this stays on the in-house kernels, which also skip the key tiles no query of a block
-    can see; off it (CPU, fp32, head dim other than 128, S % 128 != 0, PS_AMD_DISABLE=flash_attn) SDPA
+    can see; off it (CPU, fp32, head dim other than 64 or 128, S % 128 != 0, PS_AMD_DISABLE=flash_attn) SDPA
     gets the dense boolean mask [B, 1, S, S] built from doc_start."""
     if doc_bounds is None:
         if flash_ok(q, k, v):
