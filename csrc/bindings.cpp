@@ -10,6 +10,7 @@
 
 #include "psamd_launch.h"
 
+#include <array>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -1301,6 +1302,66 @@ Tensor rope_split_bwd(Tensor dq, Tensor dk, Tensor dv, Tensor cs) {
   return dqkv;
 }
 
+// Per-head QK RMSNorm + RoPE + split (csrc/kernels/rope_norm.hip): qkv / cs as rope_split_fwd, hd 64 or 128,
+// wq / wk [hd] of one dtype (fp32 or bf16).  -> the sizes {B, S, hd}
+static std::array<int64_t, 3> check_rope_norm(const Tensor& qkv, const Tensor& cs, const Tensor& wq, const Tensor& wk,
+                                              int64_t H, int64_t KV) {
+  check_rows(qkv, "qkv");
+  check_f32(cs, "cs");
+  TORCH_CHECK(H >= 1 && KV >= 1 && qkv.dim() == 4 && qkv.size(2) == H + 2 * KV, "qkv [B, S, H+2KV, hd]");
+  const int64_t B = qkv.size(0), S = qkv.size(1), hd = qkv.size(3);
+  TORCH_CHECK(hd == 64 || hd == 128, "rope_norm_split: head dim 64 or 128, got ", hd);
+  TORCH_CHECK(cs.numel() == S * hd, "cs [S, hd/2, 2]");
+  TORCH_CHECK(qkv.numel() > 0 && qkv.numel() < (int64_t(1) << 31), "rope_norm_split: qkv of 1 to 2^31 - 1 elements");
+  for (const Tensor* w : {&wq, &wk}) {
+    check_gpu(*w, "wq / wk");
+    TORCH_CHECK(w->dim() == 1 && w->size(0) == hd, "wq / wk: [hd] = [", hd, "]");
+    TORCH_CHECK(w->scalar_type() == torch::kFloat32 || w->scalar_type() == torch::kBFloat16, "wq / wk: fp32 or bf16");
+    TORCH_CHECK(al16(w->data_ptr()), "wq / wk: 16-byte aligned");
+  }
+  TORCH_CHECK(wq.scalar_type() == wk.scalar_type(), "wq and wk of one dtype");
+  TORCH_CHECK(al16(qkv.data_ptr()) && al16(cs.data_ptr()), "qkv / cs: 16-byte aligned");
+  return {B, S, hd};
+}
+
+// -> [q [B,H,S,hd], k [B,KV,S,hd], v [B,KV,S,hd]]
+std::vector<Tensor> rope_norm_split_fwd(Tensor qkv, Tensor cs, Tensor wq, Tensor wk, int64_t H, int64_t KV, double eps) {
+  const auto [B, S, hd] = check_rope_norm(qkv, cs, wq, wk, H, KV);
+  const c10::DeviceGuard guard(qkv.device());
+  auto q = torch::empty({B, H, S, hd}, qkv.options());
+  auto k = torch::empty({B, KV, S, hd}, qkv.options());
+  auto v = torch::empty({B, KV, S, hd}, qkv.options());
+  psamd::launch_rope_norm_split_fwd(u16(qkv), cs.data_ptr<float>(), wq.data_ptr(), wk.data_ptr(),
+                                    wq.scalar_type() == torch::kBFloat16, u16m(q), u16m(k), u16m(v), B, S, H, KV, hd,
+                                    static_cast<float>(eps), cur_stream(qkv));
+  return {q, k, v};
+}
+
+// -> [dqkv, dwq (fp32 [hd]), dwk (fp32 [hd])]; qkv is the forward's input (rstd is recomputed from it)
+std::vector<Tensor> rope_norm_split_bwd(Tensor dq, Tensor dk, Tensor dv, Tensor qkv, Tensor cs, Tensor wq, Tensor wk,
+                                        double eps) {
+  check_rows(dq, "dq");
+  check_rows(dk, "dk");
+  check_rows(dv, "dv");
+  TORCH_CHECK(dq.dim() == 4 && dk.dim() == 4 && dk.sizes() == dv.sizes(), "dq [B,H,S,hd], dk / dv [B,KV,S,hd]");
+  const int64_t H = dq.size(1), KV = dk.size(1);
+  const auto [B, S, hd] = check_rope_norm(qkv, cs, wq, wk, H, KV);
+  TORCH_CHECK(dq.size(0) == B && dq.size(2) == S && dq.size(3) == hd && dk.size(0) == B && dk.size(2) == S &&
+                  dk.size(3) == hd,
+              "dq / dk / dv: the forward's outputs' shapes");
+  TORCH_CHECK(al16(dq.data_ptr()) && al16(dk.data_ptr()) && al16(dv.data_ptr()), "dq / dk / dv: 16-byte aligned");
+  const c10::DeviceGuard guard(qkv.device());
+  auto dqkv = torch::empty_like(qkv);
+  auto fopt = qkv.options().dtype(torch::kFloat32);
+  auto part = torch::empty({psamd::rope_norm_bwd_parts(B, S, H, KV, hd), 2 * hd}, fopt);
+  auto dw = torch::empty({2, hd}, fopt);
+  psamd::launch_rope_norm_split_bwd(u16(dq), u16(dk), u16(dv), u16(qkv), cs.data_ptr<float>(), wq.data_ptr(),
+                                    wk.data_ptr(), wq.scalar_type() == torch::kBFloat16, u16m(dqkv),
+                                    part.data_ptr<float>(), dw.data_ptr<float>(), B, S, H, KV, hd,
+                                    static_cast<float>(eps), cur_stream(qkv));
+  return {dqkv, dw[0], dw[1]};
+}
+
 // ------------------------------------------------------------------------------ DLRM interaction
 static void check_interact(const Tensor& x, const Tensor& e) {
   check_gpu(x, "x");
@@ -2345,6 +2406,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_split_fwd", &rope_split_fwd);
   m.def("rope_split_bwd", &rope_split_bwd);
+  m.def("rope_norm_split_fwd", &rope_norm_split_fwd);
+  m.def("rope_norm_split_bwd", &rope_norm_split_bwd);
   m.def("dlrm_interact_bwd", &dlrm_interact_bwd);
   m.def("maxpool_nhwc_bwd", &maxpool_nhwc_bwd);
   m.def("pool_bn_bwd", &pool_bn_bwd);

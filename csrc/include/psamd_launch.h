@@ -310,6 +310,20 @@ void launch_rope_split_fwd(const uint16_t* qkv, const float* cs, uint16_t* q, ui
                            int H, int KV, int hd, hipStream_t st);
 void launch_rope_split_bwd(const uint16_t* dq, const uint16_t* dk, const uint16_t* dv, const float* cs,
                            uint16_t* dqkv, int B, int S, int H, int KV, int hd, hipStream_t st);
+// out[c] = sum of part[0..G)[c] in a fixed order (two launches); mid: min(G, 32) scratch rows of D
+void colsum2(const float* part, int G, int D, float* mid, float* out, hipStream_t st);
+
+// ---------------------------------------------------------------- rope_norm.hip (per-head QK RMSNorm + RoPE + split)
+// hd 64 or 128; wq / wk [hd] fp32 or bf16 (w_bf16: both); B * S * (H + 2 KV) < 2^31
+void launch_rope_norm_split_fwd(const uint16_t* qkv, const float* cs, const void* wq, const void* wk, bool w_bf16,
+                                uint16_t* q, uint16_t* k, uint16_t* v, int B, int S, int H, int KV, int hd, float eps,
+                                hipStream_t st);
+int rope_norm_bwd_parts(int B, int S, int H, int KV, int hd);  // rows of `part` ([rows, 2 * hd] fp32)
+// dw: [2, hd] fp32 (dwq | dwk)
+void launch_rope_norm_split_bwd(const uint16_t* dq, const uint16_t* dk, const uint16_t* dv, const uint16_t* qkv,
+                                const float* cs, const void* wq, const void* wk, bool w_bf16, uint16_t* dqkv,
+                                float* part, float* dw, int B, int S, int H, int KV, int hd, float eps,
+                                hipStream_t st);
 
 struct BnBwdArgs {
   const uint16_t* dy;

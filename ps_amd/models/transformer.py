@@ -237,6 +237,7 @@ class LlamaConfig:
     rope_theta: float = 500000.0
     eps: float = 1e-5
     max_seq: int = 8192
+    qk_norm: bool = False  # per-head RMSNorm of q and k before RoPE (Qwen3 / OLMo-2 / Gemma-3 style blocks)
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -247,6 +248,12 @@ class LlamaConfig:
         """The shapes of Llama-3.2-1B: head dim 64, 4 query heads per KV head.  Shapes only: the released
         checkpoint's tied input / output embeddings and its RoPE frequency scaling are not modelled."""
         return LlamaConfig(vocab=128256, hidden=2048, layers=16, heads=32, kv_heads=8, ffn=8192, rope_theta=500000.0)
+
+    @staticmethod
+    def qwen3_8b() -> "LlamaConfig":
+        """The shapes of Qwen3-8B: head dim 128, 4 query heads per KV head, QK norm.  Shapes only."""
+        return LlamaConfig(vocab=151936, hidden=4096, layers=36, heads=32, kv_heads=8, ffn=12288, rope_theta=1e6,
+                           eps=1e-6, qk_norm=True)
 
     @staticmethod
     def tiny() -> "LlamaConfig":
@@ -280,6 +287,9 @@ class LlamaBlock(nn.Module):
         self.mlp_norm = RMSNorm(c.hidden, c.eps)
         self.w13 = PsLinear(c.hidden, 2 * c.ffn, bias=False)
         self.w2 = PsLinear(c.ffn, c.hidden, bias=False)
+        if c.qk_norm:  # one [hd] weight for all query heads, one for all key heads
+            self.q_norm = nn.Parameter(torch.ones(hd))
+            self.k_norm = nn.Parameter(torch.ones(hd))
 
     def forward(self, x, r, cs, doc_bounds=None):
         """Residual stream = x + r (r: the previous block's pending MLP output, None for the
@@ -294,7 +304,10 @@ class LlamaBlock(nn.Module):
         else:
             x, h = rms_norm(x, self.attn_norm.weight, c.eps, residual=r)
         qkv = self.wqkv(h).view(b, s, c.heads + 2 * c.kv_heads, hd)
-        q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads)  # RoPE + split + transpose, one pass
+        if c.qk_norm:  # + per-head RMSNorm of q and k, still one pass (csrc/kernels/rope_norm.hip)
+            q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads, self.q_norm, self.k_norm, c.eps)
+        else:
+            q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads)  # RoPE + split + transpose, one pass
         o = self.wo(attention_causal_gqa(q, k, v, doc_bounds))  # flash kernel (heads merged) or SDPA
         x, h = rms_norm(x, self.mlp_norm.weight, c.eps, residual=o)
         return x, self.w2(swiglu(self.w13(h)))

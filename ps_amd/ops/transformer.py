@@ -4,6 +4,8 @@
   layer_norm_residual(x, o, g, b, eps, p)    -> LN(x + dropout_p(o))        (BERT post-LN)
   swiglu(gu)                                  -> silu(gu[..., :F]) * gu[..., F:]
   rope_split(qkv, cs, H, KV)                  -> q, k, v  (RoPE + head split + transpose)
+  rope_split(qkv, cs, H, KV, q_norm, k_norm)  -> the same after a per-head RMSNorm of q and k
+                                                 (csrc/kernels/rope_norm.hip, head dim 64 / 128)
   attention_qkv(qkv, H, p, mask, key_lengths) -> dropout_p(softmax(q k^T / 8)) v over the fused qkv
                                                  projection (csrc/kernels/attention.hip, S <= 128;
                                                  csrc/kernels/attention_long.hip, 128 < S <= 512;
@@ -171,13 +173,65 @@ class _RopeSplit(torch.autograd.Function):
         return native().rope_split_bwd(dq.contiguous(), dk.contiguous(), dv.contiguous(), cs), None, None, None
 
 
-def rope_split(qkv: torch.Tensor, cs: torch.Tensor, H: int, KV: int):
-    """qkv [B, S, H + 2 KV, hd] -> q [B, H, S, hd], k/v [B, KV, S, hd] with RoPE on q and k."""
-    if _hip(qkv) and qkv.shape[-1] % 16 == 0:
-        return _RopeSplit.apply(qkv, cs, H, KV)
-    x = qkv.transpose(1, 2)
-    q, k, v = x.split([H, KV, KV], dim=1)
-    return _rope_ref(q, cs), _rope_ref(k, cs), v
+def _rope_norm_ref(qkv, cs, H, KV, q_norm, k_norm, eps):
+    """The plain composition: per-head RMSNorm (fp32, or fp64 on fp64 input) times the weight, rounded to
+    qkv's dtype, then ``_rope_ref``; v untouched.  Also the yardstick of the fused kernels' GPU tests."""
+    q, k, v = qkv.transpose(1, 2).split([H, KV, KV], dim=1)
+
+    def norm(x, w):
+        xf = x.to(torch.promote_types(x.dtype, torch.float32))
+        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.to(xf.dtype)).to(x.dtype)
+
+    return _rope_ref(norm(q, q_norm), cs), _rope_ref(norm(k, k_norm), cs), v
+
+
+class _RopeNormSplit(torch.autograd.Function):
+    """csrc/kernels/rope_norm.hip: one pass each way; the backward recomputes rstd from the saved qkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, cs, wq, wk, H, KV, eps):
+        qkv = qkv.contiguous()
+        q, k, v = native().rope_norm_split_fwd(qkv, cs, wq, wk, int(H), int(KV), float(eps))
+        ctx.save_for_backward(qkv, cs, wq, wk)
+        ctx.eps = float(eps)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        qkv, cs, wq, wk = ctx.saved_tensors
+        dqkv, dwq, dwk = native().rope_norm_split_bwd(dq.contiguous(), dk.contiguous(), dv.contiguous(), qkv, cs,
+                                                      wq, wk, ctx.eps)
+        return dqkv, None, dwq.to(wq.dtype), dwk.to(wk.dtype), None, None, None
+
+
+def _norm_weight_ok(w: torch.Tensor, hd: int) -> bool:
+    return (w.is_cuda and w.dtype in (torch.bfloat16, torch.float32) and tuple(w.shape) == (hd,)
+            and w.is_contiguous() and w.data_ptr() % 16 == 0)
+
+
+def rope_split(qkv: torch.Tensor, cs: torch.Tensor, H: int, KV: int, q_norm: Optional[torch.Tensor] = None,
+               k_norm: Optional[torch.Tensor] = None, eps: float = 1e-6):
+    """qkv [B, S, H + 2 KV, hd] -> q [B, H, S, hd], k/v [B, KV, S, hd] with RoPE on q and k.
+
+    ``q_norm`` / ``k_norm`` [hd] (both or neither; ``ValueError`` otherwise): per-head QK RMSNorm before
+    the rotation (Qwen3 / OLMo-2 / Gemma-3 style) -- every query head row x becomes
+    ``x * rsqrt(mean(x^2) + eps) * q_norm``, every key head row the same with ``k_norm``; one weight is
+    shared by all heads of its kind and v is untouched.  GPU bf16 at head dim 64 or 128 (the flash domain)
+    with fp32 or bf16 weights runs the fused kernels of csrc/kernels/rope_norm.hip; anything else the
+    torch composition ``_rope_norm_ref``."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_split: give q_norm and k_norm, or neither")
+    if q_norm is None:
+        if _hip(qkv) and qkv.shape[-1] % 16 == 0:
+            return _RopeSplit.apply(qkv, cs, H, KV)
+        x = qkv.transpose(1, 2)
+        q, k, v = x.split([H, KV, KV], dim=1)
+        return _rope_ref(q, cs), _rope_ref(k, cs), v
+    hd = qkv.shape[-1]
+    if (_hip(qkv) and hd in (64, 128) and 0 < qkv.numel() < 2 ** 31 and q_norm.dtype == k_norm.dtype
+            and _norm_weight_ok(q_norm, hd) and _norm_weight_ok(k_norm, hd)):
+        return _RopeNormSplit.apply(qkv, cs, q_norm, k_norm, H, KV, eps)
+    return _rope_norm_ref(qkv, cs, H, KV, q_norm, k_norm, eps)
 
 
 # ------------------------------------------------------------------------------ attention
