@@ -1362,6 +1362,132 @@ std::vector<Tensor> rope_norm_split_bwd(Tensor dq, Tensor dk, Tensor dv, Tensor 
   return {dqkv, dw[0], dw[1]};
 }
 
+// ------------------------------------------------------------------------------ mixture-of-experts FFN (moe.hip)
+static void check_i32(const Tensor& t, const char* n) {
+  check_gpu(t, n);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, n, " must be int32");
+}
+static const int* i32(const Tensor& t) { return t.data_ptr<int>(); }
+
+// The plan's tensors as the other moe ops take them: {row_token, row_slot [R_cap], slot_row [T, k],
+// tile_expert [R_cap / tile], counts, seg [E]}.  -> {T, k, E, tiles}
+static std::array<int64_t, 4> check_moe_plan(const std::vector<Tensor>& plan) {
+  TORCH_CHECK(plan.size() == 6, "moe: plan is the 6 tensors of moe_plan");
+  for (const Tensor& t : plan) check_i32(t, "moe plan tensor");
+  const Tensor &row_token = plan[0], &row_slot = plan[1], &slot_row = plan[2], &tile_expert = plan[3];
+  TORCH_CHECK(slot_row.dim() == 2, "moe: slot_row [T, k]");
+  const int64_t T = slot_row.size(0), k = slot_row.size(1), E = plan[4].numel(), tiles = tile_expert.numel();
+  TORCH_CHECK(E >= 1 && E <= psamd::kMoeMaxExperts && plan[5].numel() == E, "moe: counts / seg [E], E <= 128");
+  TORCH_CHECK(k >= 1 && k <= psamd::kMoeMaxTopK && T >= 1, "moe: slot_row [T >= 1, 1 <= k <= 8]");
+  TORCH_CHECK(tiles == psamd::moe_row_tiles(T, static_cast<int>(k), static_cast<int>(E)) &&
+                  row_token.numel() == tiles * psamd::kMoeRowTile && row_slot.numel() == row_token.numel(),
+              "moe: plan sizes do not belong together");
+  return {T, k, E, tiles};
+}
+
+// idx [T, k] int32 / int64 (ids off [0, E) map to no row) -> {row_token, row_slot, slot_row, tile_expert, counts, seg}
+std::vector<Tensor> moe_plan(Tensor idx, int64_t E) {
+  check_gpu(idx, "idx");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt32 || idx.scalar_type() == torch::kInt64, "moe_plan: idx int32 or int64");
+  TORCH_CHECK(idx.dim() == 2, "moe_plan: idx [T, k]");
+  const int64_t T = idx.size(0), k = idx.size(1);
+  TORCH_CHECK(E >= 1 && E <= psamd::kMoeMaxExperts, "moe_plan: 1 <= E <= 128, got ", E);
+  TORCH_CHECK(k >= 1 && k <= psamd::kMoeMaxTopK, "moe_plan: 1 <= k <= 8, got ", k);
+  TORCH_CHECK(T >= 1 && T * k + (E + 1) * psamd::kMoeRowTile < (int64_t(1) << 31), "moe_plan: 1 <= T, T * k < 2^31");
+  const c10::DeviceGuard guard(idx.device());
+  auto iopt = idx.options().dtype(torch::kInt32);
+  const int64_t tiles = psamd::moe_row_tiles(T, static_cast<int>(k), static_cast<int>(E));
+  auto row_token = torch::empty({tiles * psamd::kMoeRowTile}, iopt), row_slot = torch::empty_like(row_token);
+  auto slot_row = torch::empty({T, k}, iopt), tile_expert = torch::empty({tiles}, iopt);
+  auto counts = torch::empty({E}, iopt), seg = torch::empty({E}, iopt);
+  auto hist = torch::empty({psamd::moe_plan_chunks(T * k), E}, iopt);
+  psamd::launch_moe_plan(idx.data_ptr(), idx.scalar_type() == torch::kInt64, T, static_cast<int>(k),
+                         static_cast<int>(E), hist.data_ptr<int>(), row_token.data_ptr<int>(), row_slot.data_ptr<int>(),
+                         slot_row.data_ptr<int>(), tile_expert.data_ptr<int>(), counts.data_ptr<int>(),
+                         seg.data_ptr<int>(), cur_stream(idx));
+  return {row_token, row_slot, slot_row, tile_expert, counts, seg};
+}
+
+static const float* moe_wts(const c10::optional<Tensor>& wts, int64_t T, int64_t k) {
+  if (!has(wts)) return nullptr;
+  check_f32(*wts, "wts");
+  TORCH_CHECK(wts->dim() == 2 && wts->size(0) == T && wts->size(1) == k, "moe: wts [T, k]");
+  return wts->data_ptr<float>();
+}
+
+// c [R_cap, N] = A' . op(w[expert of the row tile]).  gather: a is [T, K] and row r reads a[row_token[r]] (times
+// wts[row_slot[r]] when wts is given); else a is [R_cap, K].  w [E, N, K], or with nn [E, K, N].
+Tensor moe_gemm(Tensor a, Tensor w, std::vector<Tensor> plan, bool gather, c10::optional<Tensor> wts, bool nn) {
+  const auto [T, k, E, tiles] = check_moe_plan(plan);
+  check_rows(a, "a");
+  check_rows(w, "w");
+  TORCH_CHECK(a.dim() == 2 && w.dim() == 3 && w.size(0) == E, "moe_gemm: a [rows, K], w [E, ., .]");
+  const int64_t K = a.size(1), N = nn ? w.size(2) : w.size(1);
+  TORCH_CHECK((nn ? w.size(1) : w.size(2)) == K, "moe_gemm: w's reduction length is a's row length");
+  TORCH_CHECK(K % 64 == 0 && N % 64 == 0 && K >= 64 && N >= 64 && K * N < (int64_t(1) << 31), "moe_gemm: K % 64, N % 64");
+  TORCH_CHECK(a.size(0) == (gather ? T : tiles * psamd::kMoeRowTile), "moe_gemm: a has T rows (gather) or R_cap rows");
+  TORCH_CHECK(gather || !has(wts), "moe_gemm: wts only with gather");
+  const float* wp = moe_wts(wts, T, k);
+  TORCH_CHECK(al16(a.data_ptr()) && al16(w.data_ptr()), "moe_gemm: 16-byte aligned");
+  const c10::DeviceGuard guard(a.device());
+  auto c = torch::empty({tiles * psamd::kMoeRowTile, N}, a.options());
+  psamd::launch_moe_gemm(u16(a), gather ? i32(plan[0]) : nullptr, i32(plan[1]), wp, u16(w), i32(plan[3]), u16m(c),
+                         static_cast<int>(tiles), static_cast<int>(N), static_cast<int>(K), nn, cur_stream(a));
+  return c;
+}
+
+// dw [E, Nn, Cc] = per expert sum over its rows of G'[r, n] A'[r, c].  gathered: 0 none, 1 g is [T, Nn] read
+// through row_token (times wts[row_slot] when given), 2 a is [T, Cc] likewise; the other operand has R_cap rows.
+Tensor moe_wgrad(Tensor g, Tensor a, std::vector<Tensor> plan, int64_t gathered, c10::optional<Tensor> wts) {
+  const auto [T, k, E, tiles] = check_moe_plan(plan);
+  check_rows(g, "g");
+  check_rows(a, "a");
+  TORCH_CHECK(gathered >= 0 && gathered <= 2 && g.dim() == 2 && a.dim() == 2, "moe_wgrad: g [., Nn], a [., Cc]");
+  const int64_t Nn = g.size(1), Cc = a.size(1), R = tiles * psamd::kMoeRowTile;
+  TORCH_CHECK(Nn % 64 == 0 && Cc % 64 == 0 && Nn >= 64 && Cc >= 64 && Nn * Cc < (int64_t(1) << 31), "moe_wgrad: Nn % 64, Cc % 64");
+  TORCH_CHECK(g.size(0) == (gathered == 1 ? T : R) && a.size(0) == (gathered == 2 ? T : R),
+              "moe_wgrad: the gathered operand has T rows, the other R_cap");
+  TORCH_CHECK(gathered != 0 || !has(wts), "moe_wgrad: wts only with a gathered operand");
+  const float* wp = moe_wts(wts, T, k);
+  TORCH_CHECK(al16(g.data_ptr()) && al16(a.data_ptr()), "moe_wgrad: 16-byte aligned");
+  const c10::DeviceGuard guard(g.device());
+  auto dw = torch::empty({E, Nn, Cc}, g.options());
+  psamd::launch_moe_wgrad(u16(g), u16(a), static_cast<int>(gathered), i32(plan[0]), i32(plan[1]), wp, i32(plan[5]),
+                          i32(plan[4]), u16m(dw), static_cast<int>(E), static_cast<int>(Nn), static_cast<int>(Cc),
+                          cur_stream(g));
+  return dw;
+}
+
+// out [T, D] = sum_j wts[t, j] y[slot_row[t, j]] (no wts: the plain sum)
+Tensor moe_combine(Tensor y, std::vector<Tensor> plan, c10::optional<Tensor> wts) {
+  const auto [T, k, E, tiles] = check_moe_plan(plan);
+  check_rows(y, "y");
+  TORCH_CHECK(y.dim() == 2 && y.size(0) == tiles * psamd::kMoeRowTile && y.size(1) % 8 == 0 && al16(y.data_ptr()),
+              "moe_combine: y [R_cap, D], D % 8");
+  const float* wp = moe_wts(wts, T, k);
+  const c10::DeviceGuard guard(y.device());
+  auto out = torch::empty({T, y.size(1)}, y.options());
+  psamd::launch_moe_combine(u16(y), i32(plan[2]), wp, u16m(out), T, static_cast<int>(k), static_cast<int>(y.size(1)),
+                            cur_stream(y));
+  return out;
+}
+
+// dwts [T, k] fp32 = <y[slot_row[t, j]], dout[t]>
+Tensor moe_combine_bwd(Tensor y, std::vector<Tensor> plan, Tensor dout) {
+  const auto [T, k, E, tiles] = check_moe_plan(plan);
+  check_rows(y, "y");
+  check_rows(dout, "dout");
+  TORCH_CHECK(y.dim() == 2 && y.size(0) == tiles * psamd::kMoeRowTile && y.size(1) % 8 == 0 && al16(y.data_ptr()),
+              "moe_combine_bwd: y [R_cap, D], D % 8");
+  TORCH_CHECK(dout.dim() == 2 && dout.size(0) == T && dout.size(1) == y.size(1) && al16(dout.data_ptr()),
+              "moe_combine_bwd: dout [T, D]");
+  const c10::DeviceGuard guard(y.device());
+  auto dwts = torch::empty({T, k}, y.options().dtype(torch::kFloat32));
+  psamd::launch_moe_combine_bwd(u16(y), i32(plan[2]), u16(dout), dwts.data_ptr<float>(), T, static_cast<int>(k),
+                                static_cast<int>(y.size(1)), cur_stream(y));
+  return dwts;
+}
+
 // ------------------------------------------------------------------------------ DLRM interaction
 static void check_interact(const Tensor& x, const Tensor& e) {
   check_gpu(x, "x");
@@ -2408,6 +2534,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_split_bwd", &rope_split_bwd);
   m.def("rope_norm_split_fwd", &rope_norm_split_fwd);
   m.def("rope_norm_split_bwd", &rope_norm_split_bwd);
+  m.def("moe_plan", &moe_plan);
+  m.def("moe_gemm", &moe_gemm);
+  m.def("moe_wgrad", &moe_wgrad);
+  m.def("moe_combine", &moe_combine);
+  m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("dlrm_interact_bwd", &dlrm_interact_bwd);
   m.def("maxpool_nhwc_bwd", &maxpool_nhwc_bwd);
   m.def("pool_bn_bwd", &pool_bn_bwd);

@@ -325,6 +325,34 @@ void launch_rope_norm_split_bwd(const uint16_t* dq, const uint16_t* dk, const ui
                                 float* part, float* dw, int B, int S, int H, int KV, int hd, float eps,
                                 hipStream_t st);
 
+// ---------------------------------------------------------------- moe.hip (mixture-of-experts FFN)
+constexpr int kMoeRowTile = 128;     // rows per GEMM tile: every expert's segment starts at a multiple of it
+constexpr int kMoeMaxExperts = 128;
+constexpr int kMoeMaxTopK = 8;
+// row tiles of the permuted row space (R_cap = tiles * kMoeRowTile), from the sizes alone: sum_e ceil(c_e / tile)
+// <= floor(T k / tile) + E for any routing
+inline int moe_row_tiles(int64_t T, int k, int E) {
+  return static_cast<int>((T * k + kMoeRowTile - 1) / kMoeRowTile) + E;
+}
+int moe_plan_chunks(int64_t n);  // rows of `hist` ([chunks, E] int32) for n = T * k pairs
+// idx [T, k] int32 / int64; row_token, row_slot [R_cap]; slot_row [T, k]; tile_expert [tiles]; counts, seg [E]
+void launch_moe_plan(const void* idx, bool idx_i64, int64_t T, int k, int E, int* hist, int* row_token, int* row_slot,
+                     int* slot_row, int* tile_expert, int* counts, int* seg, hipStream_t st);
+// c [R_cap, N] = A' . op(w[tile_expert]); a [R_cap, K], or (row_token given) gathered rows of a [T, K], times
+// wts[row_slot] when wts is given too; w [E, N, K] (nn false) or [E, K, N] (nn true); N % 64 == 0, K % 64 == 0
+void launch_moe_gemm(const uint16_t* a, const int* row_token, const int* row_slot, const float* wts, const uint16_t* w,
+                     const int* tile_expert, uint16_t* c, int n_tiles, int N, int K, bool nn, hipStream_t st);
+// dw [E, Nn, Cc] = per expert G'^T A' over its rows; gathered: 0 none, 1 g is [T, Nn] read through row_token
+// (times wts[row_slot] when given), 2 a is [T, Cc] likewise; Nn % 64 == 0, Cc % 64 == 0
+void launch_moe_wgrad(const uint16_t* g, const uint16_t* a, int gathered, const int* row_token, const int* row_slot,
+                      const float* wts, const int* seg, const int* counts, uint16_t* dw, int E, int Nn, int Cc,
+                      hipStream_t st);
+// out [T, D] = sum_j wts[t, j] y[slot_row[t, j]] (wts null: the plain sum); D % 8 == 0
+void launch_moe_combine(const uint16_t* y, const int* slot_row, const float* wts, uint16_t* out, int64_t T, int k, int D,
+                        hipStream_t st);
+void launch_moe_combine_bwd(const uint16_t* y, const int* slot_row, const uint16_t* dout, float* dwts, int64_t T, int k,
+                            int D, hipStream_t st);
+
 struct BnBwdArgs {
   const uint16_t* dy;
   const uint16_t* y;          // nullable when mask_coef is given (relu, no residual)

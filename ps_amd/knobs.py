@@ -36,6 +36,7 @@ ROUTES: Dict[str, str] = {
     "fused_attn": "BERT attention (S <= 512) on SDPA (key_lengths of a right-padded batch as a boolean key mask)",
     "flash_attn": "causal GQA attention on SDPA",
     "fused_xent": "cross-entropy on fp32 logits through F.cross_entropy",
+    "moe_ffn": "the mixture-of-experts FFN as the torch loop over experts (ops/moe.py _moe_ref)",
     # sparse rows (ops/sparse.py)
     "bag_pool": "multi-hot bags pooled by gather_rows -> weight multiply -> segment_reduce_rows ([nnz, dim] in HBM)",
 }

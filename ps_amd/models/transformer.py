@@ -24,6 +24,7 @@ from torch.utils.checkpoint import checkpoint
 
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
+from ..ops.moe import moe_ffn, route as moe_route
 from ..ops.transformer import (PackedSeqs, attention_causal_gqa, attention_qkv, cross_entropy,
                               doc_bounds as _doc_bounds, layer_norm_residual, pack_seqs, rms_norm, rope_split,
                               rope_table, swiglu)
@@ -238,6 +239,12 @@ class LlamaConfig:
     eps: float = 1e-5
     max_seq: int = 8192
     qk_norm: bool = False  # per-head RMSNorm of q and k before RoPE (Qwen3 / OLMo-2 / Gemma-3 style blocks)
+    # mixture-of-experts FFN (ops/moe.py): 0 experts = the dense SwiGLU FFN.  moe_ffn: the experts' FFN width
+    # (0: ``ffn``); moe_norm_topk: the k routing weights renormalised to sum 1
+    moe_experts: int = 0
+    moe_top_k: int = 2
+    moe_ffn: int = 0
+    moe_norm_topk: bool = True
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -256,8 +263,19 @@ class LlamaConfig:
                            eps=1e-6, qk_norm=True)
 
     @staticmethod
+    def mixtral_8x7b() -> "LlamaConfig":
+        """The shapes of Mixtral-8x7B: 8 experts of FFN width 14336, top 2 renormalised.  Shapes only."""
+        return LlamaConfig(vocab=32000, hidden=4096, layers=32, heads=32, kv_heads=8, ffn=14336, rope_theta=1e6,
+                           moe_experts=8, moe_top_k=2)
+
+    @staticmethod
     def tiny() -> "LlamaConfig":
         return LlamaConfig(vocab=512, hidden=64, layers=2, heads=4, kv_heads=2, ffn=128, max_seq=128)
+
+    @staticmethod
+    def tiny_moe() -> "LlamaConfig":
+        return LlamaConfig(vocab=512, hidden=64, layers=2, heads=4, kv_heads=2, ffn=128, max_seq=128, moe_experts=4,
+                           moe_top_k=2, moe_ffn=64)
 
 
 class RMSNorm(nn.Module):
@@ -274,7 +292,8 @@ class LlamaBlock(nn.Module):
     """Pre-norm decoder block.  Q/K/V and gate/up projections are single fused GEMMs
     (``wqkv`` [(H + 2 KV) * hd, D], ``w13`` [2 F, D] -- same parameter count as separate
     matrices, one hipBLASLt launch each); attention is the causal GQA flash kernel
-    (csrc/kernels/flash_attn.hip; no K/V replication, output already head-merged)."""
+    (csrc/kernels/flash_attn.hip; no K/V replication, output already head-merged).  With ``c.moe_experts`` the FFN
+    is a mixture of experts: ``router`` + stacked ``w13_e`` [E, 2 F, D] / ``w2_e`` [E, D, F] through ``ops.moe.moe_ffn``."""
 
     def __init__(self, c: LlamaConfig):
         super().__init__()
@@ -285,8 +304,14 @@ class LlamaBlock(nn.Module):
         self.wqkv = PsLinear(c.hidden, (c.heads + 2 * c.kv_heads) * hd, bias=False)
         self.wo = PsLinear(c.heads * hd, c.hidden, bias=False)
         self.mlp_norm = RMSNorm(c.hidden, c.eps)
-        self.w13 = PsLinear(c.hidden, 2 * c.ffn, bias=False)
-        self.w2 = PsLinear(c.ffn, c.hidden, bias=False)
+        if c.moe_experts:  # router + stacked expert weights (plain parameters, other names than the dense FFN's)
+            f = c.moe_ffn or c.ffn
+            self.router = nn.Linear(c.hidden, c.moe_experts, bias=False)
+            self.w13_e = nn.Parameter(torch.empty(c.moe_experts, 2 * f, c.hidden).normal_(std=0.02))
+            self.w2_e = nn.Parameter(torch.empty(c.moe_experts, c.hidden, f).normal_(std=0.02))
+        else:
+            self.w13 = PsLinear(c.hidden, 2 * c.ffn, bias=False)
+            self.w2 = PsLinear(c.ffn, c.hidden, bias=False)
         if c.qk_norm:  # one [hd] weight for all query heads, one for all key heads
             self.q_norm = nn.Parameter(torch.ones(hd))
             self.k_norm = nn.Parameter(torch.ones(hd))
@@ -310,6 +335,10 @@ class LlamaBlock(nn.Module):
             q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads)  # RoPE + split + transpose, one pass
         o = self.wo(attention_causal_gqa(q, k, v, doc_bounds))  # flash kernel (heads merged) or SDPA
         x, h = rms_norm(x, self.mlp_norm.weight, c.eps, residual=o)
+        if c.moe_experts:  # routing in torch on [T, E]; the experts on the grouped kernels (csrc/kernels/moe.hip)
+            hf = h.reshape(b * s, c.hidden)
+            idx, wts = moe_route(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk)
+            return x, moe_ffn(hf, idx, wts, self.w13_e, self.w2_e).view(b, s, c.hidden)
         return x, self.w2(swiglu(self.w13(h)))
 
 
