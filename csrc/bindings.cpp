@@ -1488,6 +1488,52 @@ Tensor moe_combine_bwd(Tensor y, std::vector<Tensor> plan, Tensor dout) {
   return dwts;
 }
 
+// ------------------------------------------------------------------------------ LM-head loss without the logits (lm_head.hip)
+static std::array<int64_t, 3> check_lm_head(const Tensor& h, const Tensor& w, const Tensor& lab) {
+  check_rows(h, "h");
+  check_rows(w, "w");
+  check_gpu(lab, "labels");
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && h.size(1) == w.size(1), "lm_head: h [T, D], w [V, D]");
+  const int64_t T = h.size(0), D = h.size(1), V = w.size(0);
+  TORCH_CHECK(T >= 1 && D >= 64 && D % 64 == 0 && V >= 8 && V % 8 == 0, "lm_head: T >= 1, D % 64 == 0, V % 8 == 0");
+  TORCH_CHECK(T < (int64_t(1) << 31) - 128 && V < (int64_t(1) << 31) - 128, "lm_head: T, V < 2^31");
+  TORCH_CHECK(lab.scalar_type() == torch::kInt64 && lab.dim() == 1 && lab.numel() == T, "lm_head: labels [T] int64");
+  TORCH_CHECK(al16(h.data_ptr()) && al16(w.data_ptr()), "lm_head: 16-byte aligned");
+  return {T, D, V};
+}
+
+// -> {lse [T], loss_row [T]} fp32; ns: vocabulary splits (0: automatic)
+std::vector<Tensor> lm_head_fwd(Tensor h, Tensor w, Tensor lab, int64_t ignore, int64_t ns) {
+  const auto [T, D, V] = check_lm_head(h, w, lab);
+  TORCH_CHECK(ns >= 0 && ns <= 65536, "lm_head_fwd: 0 <= ns <= 65536");
+  const c10::DeviceGuard guard(h.device());
+  const int n = psamd::lm_head_splits(static_cast<int>(T), static_cast<int>(V), static_cast<int>(ns));
+  auto fopt = h.options().dtype(torch::kFloat32);
+  auto part = torch::empty({2, 4 * n, T}, fopt), zlab = torch::empty({T}, fopt);
+  auto lse = torch::empty({T}, fopt), loss = torch::empty({T}, fopt);
+  psamd::launch_lm_head_fwd(u16(h), u16(w), lab.data_ptr<int64_t>(), ignore, static_cast<int>(T), static_cast<int>(V),
+                            static_cast<int>(D), n, part.data_ptr<float>(), zlab.data_ptr<float>(), lse.data_ptr<float>(), loss.data_ptr<float>(), cur_stream(h));
+  return {lse, loss};
+}
+
+// dz [T, C] (bf16, written in place) = the softmax gradient of the vocabulary columns [v0, v0 + C)
+void lm_head_dz(Tensor h, Tensor w, Tensor lab, Tensor lse, Tensor go, Tensor count, int64_t ignore, int64_t v0,
+                Tensor dz) {
+  const auto [T, D, V] = check_lm_head(h, w, lab);
+  check_f32(lse, "lse");
+  check_f32(go, "go");
+  check_f32(count, "count");
+  check_rows(dz, "dz");
+  TORCH_CHECK(lse.numel() == T && go.numel() == 1 && count.numel() == 1, "lm_head_dz: lse [T], go / count scalars");
+  TORCH_CHECK(dz.dim() == 2 && dz.size(0) == T && al16(dz.data_ptr()), "lm_head_dz: dz [T, C]");
+  const int64_t C = dz.size(1);
+  TORCH_CHECK(v0 >= 0 && v0 % 8 == 0 && C >= 8 && C % 8 == 0 && v0 + C <= V, "lm_head_dz: v0 % 8, C % 8, v0 + C <= V");
+  const c10::DeviceGuard guard(h.device());
+  psamd::launch_lm_head_dz(u16(h), u16(w), lab.data_ptr<int64_t>(), ignore, lse.data_ptr<float>(), go.data_ptr<float>(),
+                           count.data_ptr<float>(), static_cast<int>(T), static_cast<int>(V), static_cast<int>(D),
+                           static_cast<int>(v0), static_cast<int>(C), u16m(dz), cur_stream(h));
+}
+
 // ------------------------------------------------------------------------------ DLRM interaction
 static void check_interact(const Tensor& x, const Tensor& e) {
   check_gpu(x, "x");
@@ -2539,6 +2585,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_wgrad", &moe_wgrad);
   m.def("moe_combine", &moe_combine);
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("lm_head_fwd", &lm_head_fwd, py::arg("h"), py::arg("w"), py::arg("labels"), py::arg("ignore_index"),
+        py::arg("ns") = 0);
+  m.def("lm_head_dz", &lm_head_dz);
   m.def("dlrm_interact_bwd", &dlrm_interact_bwd);
   m.def("maxpool_nhwc_bwd", &maxpool_nhwc_bwd);
   m.def("pool_bn_bwd", &pool_bn_bwd);

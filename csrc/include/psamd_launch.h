@@ -353,6 +353,20 @@ void launch_moe_combine(const uint16_t* y, const int* slot_row, const float* wts
 void launch_moe_combine_bwd(const uint16_t* y, const int* slot_row, const uint16_t* dout, float* dwts, int64_t T, int k,
                             int D, hipStream_t st);
 
+// ---------------------------------------------------------------- lm_head.hip (LM-head loss without the logits)
+// h [T, D], w [V, D] bf16, lab [T] int64; D % 64 == 0, V % 8 == 0.  A scored row: label != ignore and in [0, V).
+// vocabulary splits the forward runs for a request of ns (0: automatic): at most one per 128-column tile, none empty
+int lm_head_splits(int T, int V, int ns);
+// ns = lm_head_splits(...); part [2, 4 ns, T] and zlab [T] are work space; lse [T]; loss_row [T] = lse - z[label]
+// (0 for a row that is not scored)
+void launch_lm_head_fwd(const uint16_t* h, const uint16_t* w, const int64_t* lab, int64_t ignore, int T, int V, int D,
+                        int ns, float* part, float* zlab, float* lse, float* loss_row, hipStream_t st);
+// dz [T, C] = (softmax(h w^T)[:, v0 : v0 + C] - onehot) * go / max(count, 1), 0 for a row that is not scored;
+// go, count: device scalars; v0 % 8 == 0, C % 8 == 0, v0 + C <= V
+void launch_lm_head_dz(const uint16_t* h, const uint16_t* w, const int64_t* lab, int64_t ignore, const float* lse,
+                       const float* go, const float* count, int T, int V, int D, int v0, int C, uint16_t* dz,
+                       hipStream_t st);
+
 struct BnBwdArgs {
   const uint16_t* dy;
   const uint16_t* y;          // nullable when mask_coef is given (relu, no residual)

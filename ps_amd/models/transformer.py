@@ -24,6 +24,7 @@ from torch.utils.checkpoint import checkpoint
 
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
+from ..ops.lm_head import linear_cross_entropy
 from ..ops.moe import moe_ffn, route as moe_route
 from ..ops.transformer import (PackedSeqs, attention_causal_gqa, attention_qkv, cross_entropy,
                               doc_bounds as _doc_bounds, layer_norm_residual, pack_seqs, rms_norm, rope_split,
@@ -245,6 +246,9 @@ class LlamaConfig:
     moe_top_k: int = 2
     moe_ffn: int = 0
     moe_norm_topk: bool = True
+    # with labels, the loss straight from the last hidden states and lm_head.weight, no [B*S, vocab] logits or
+    # gradient in memory (ops/lm_head.py); opt-in: it trades time for that memory (profiles/lm_head_probe.txt)
+    fused_head: bool = False
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -376,14 +380,15 @@ class LlamaForCausalLM(nn.Module):
             else:
                 x, r = layer(x, r, cs, bounds)
         _, h = rms_norm(x, self.norm.weight, self.c.eps, residual=r)
-        logits = self.lm_head(h)
         if labels is None:
-            return logits
+            return self.lm_head(h)
         # next-token targets; the last position has none (ignored) -- no sliced copy of the logits
         tgt = torch.cat([labels[:, 1:], torch.full_like(labels[:, :1], -100)], dim=1)
         if doc_ids is not None:  # nor has a document's last position
             tgt[:, :-1].masked_fill_(doc_ids[:, 1:] != doc_ids[:, :-1], -100)
-        return cross_entropy(logits, tgt, ignore_index=-100)
+        if self.c.fused_head:
+            return linear_cross_entropy(h, self.lm_head.weight, tgt, ignore_index=-100)
+        return cross_entropy(self.lm_head(h), tgt, ignore_index=-100)
 
 
 def packed_lm_batch(batch: int, seq: int, vocab: int, doc_lengths, seed: int = 0, device=None):
