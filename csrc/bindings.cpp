@@ -1488,6 +1488,76 @@ Tensor moe_combine_bwd(Tensor y, std::vector<Tensor> plan, Tensor dout) {
   return dwts;
 }
 
+// ------------------------------------------------------------------------------ fused MoE router (moe_router.hip)
+// h [T, D], w [E, D] bf16 -> {idx [T, k] int64, wts [T, k], lse [T], logits [T, E], part [blocks, 2 E + 1]} (fp32);
+// row_tile: 0 (automatic), 32 or 64
+std::vector<Tensor> moe_router_fwd(Tensor h, Tensor w, int64_t k, bool norm_topk, int64_t row_tile) {
+  check_rows(h, "h");
+  check_rows(w, "w");
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && h.size(1) == w.size(1), "moe_router_fwd: h [T, D], w [E, D]");
+  const int64_t T = h.size(0), D = h.size(1), E = w.size(0);
+  TORCH_CHECK(E >= 1 && E <= psamd::kMoeMaxExperts, "moe_router_fwd: 1 <= E <= 128, got ", E);
+  TORCH_CHECK(k >= 1 && k <= psamd::kMoeMaxTopK && k <= E, "moe_router_fwd: 1 <= k <= min(8, E), got ", k);
+  TORCH_CHECK(D >= 64 && D % 64 == 0, "moe_router_fwd: D % 64 == 0, got ", D);
+  TORCH_CHECK(T >= 1 && T < (int64_t(1) << 31) - 64, "moe_router_fwd: 1 <= T < 2^31");
+  TORCH_CHECK(row_tile == 0 || row_tile == 32 || row_tile == 64, "moe_router_fwd: row_tile 0, 32 or 64");
+  TORCH_CHECK(al16(h.data_ptr()) && al16(w.data_ptr()), "moe_router_fwd: 16-byte aligned");
+  const c10::DeviceGuard guard(h.device());
+  auto fopt = h.options().dtype(torch::kFloat32);
+  const int rt = static_cast<int>(row_tile), blocks = psamd::moe_router_blocks(static_cast<int>(T), rt);
+  auto idx = torch::empty({T, k}, h.options().dtype(torch::kInt64)), wts = torch::empty({T, k}, fopt);
+  auto lse = torch::empty({T}, fopt), logits = torch::empty({T, E}, fopt), part = torch::empty({blocks, 2 * E + 1}, fopt);
+  psamd::launch_moe_router_fwd(u16(h), u16(w), static_cast<int>(T), static_cast<int>(E), static_cast<int>(D),
+                               static_cast<int>(k), norm_topk, rt, idx.data_ptr<int64_t>(), wts.data_ptr<float>(),
+                               lse.data_ptr<float>(), logits.data_ptr<float>(), part.data_ptr<float>(), cur_stream(h));
+  return {idx, wts, lse, logits, part};
+}
+
+// part of moe_router_fwd over T tokens and k slots -> {counts [E] int32, psum [E], stats [3] = lb, zl, aux}
+std::vector<Tensor> moe_router_finish(Tensor part, int64_t T, int64_t k, double aux_coef, double z_coef) {
+  check_f32(part, "part");
+  TORCH_CHECK(part.dim() == 2 && part.size(0) >= 1 && part.size(1) % 2 == 1, "moe_router_finish: part [blocks, 2 E + 1]");
+  const int64_t E = part.size(1) / 2;
+  TORCH_CHECK(E >= 1 && E <= psamd::kMoeMaxExperts, "moe_router_finish: 1 <= E <= 128, got ", E);
+  TORCH_CHECK(k >= 1 && k <= psamd::kMoeMaxTopK && k <= E, "moe_router_finish: 1 <= k <= min(8, E), got ", k);
+  TORCH_CHECK(T >= 1 && part.size(0) <= T && T < (int64_t(1) << 31) - 64, "moe_router_finish: a block per row tile of T");
+  const c10::DeviceGuard guard(part.device());
+  auto counts = torch::empty({E}, part.options().dtype(torch::kInt32));
+  auto psum = torch::empty({E}, part.options()), stats = torch::empty({3}, part.options());
+  psamd::launch_moe_router_finish(part.data_ptr<float>(), static_cast<int>(part.size(0)), static_cast<int>(T),
+                                  static_cast<int>(E), static_cast<int>(k), static_cast<float>(aux_coef),
+                                  static_cast<float>(z_coef), counts.data_ptr<int>(), psum.data_ptr<float>(),
+                                  stats.data_ptr<float>(), cur_stream(part));
+  return {counts, psum, stats};
+}
+
+// dz [T, E] bf16: the gradient of the logits from dwts [T, k] and daux (one element)
+Tensor moe_router_bwd(Tensor logits, Tensor lse, Tensor idx, Tensor wts, Tensor dwts, Tensor daux, Tensor counts,
+                      bool norm_topk, double aux_coef, double z_coef) {
+  check_f32(logits, "logits");
+  check_f32(lse, "lse");
+  check_f32(wts, "wts");
+  check_f32(dwts, "dwts");
+  check_f32(daux, "daux");
+  check_gpu(idx, "idx");
+  check_i32(counts, "counts");
+  TORCH_CHECK(logits.dim() == 2 && idx.dim() == 2 && idx.scalar_type() == torch::kInt64, "moe_router_bwd: logits [T, E], idx [T, k] int64");
+  const int64_t T = logits.size(0), E = logits.size(1), k = idx.size(1);
+  TORCH_CHECK(E >= 1 && E <= psamd::kMoeMaxExperts, "moe_router_bwd: 1 <= E <= 128, got ", E);
+  TORCH_CHECK(k >= 1 && k <= psamd::kMoeMaxTopK && k <= E, "moe_router_bwd: 1 <= k <= min(8, E), got ", k);
+  TORCH_CHECK(T >= 1 && T < (int64_t(1) << 31) - 64, "moe_router_bwd: 1 <= T < 2^31");
+  TORCH_CHECK(idx.size(0) == T && lse.numel() == T && wts.sizes() == idx.sizes() && dwts.sizes() == idx.sizes() &&
+                  daux.numel() == 1 && counts.numel() == E,
+              "moe_router_bwd: lse [T], wts / dwts [T, k], daux a scalar, counts [E]");
+  const c10::DeviceGuard guard(logits.device());
+  auto dz = torch::empty({T, E}, logits.options().dtype(torch::kBFloat16));
+  psamd::launch_moe_router_bwd(logits.data_ptr<float>(), lse.data_ptr<float>(), idx.data_ptr<int64_t>(),
+                               wts.data_ptr<float>(), dwts.data_ptr<float>(), daux.data_ptr<float>(), i32(counts),
+                               static_cast<int>(T), static_cast<int>(E), static_cast<int>(k), norm_topk,
+                               static_cast<float>(aux_coef), static_cast<float>(z_coef), u16m(dz), cur_stream(logits));
+  return dz;
+}
+
 // ------------------------------------------------------------------------------ LM-head loss without the logits (lm_head.hip)
 static std::array<int64_t, 3> check_lm_head(const Tensor& h, const Tensor& w, const Tensor& lab) {
   check_rows(h, "h");
@@ -2585,6 +2655,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_wgrad", &moe_wgrad);
   m.def("moe_combine", &moe_combine);
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("moe_router_fwd", &moe_router_fwd, py::arg("h"), py::arg("w"), py::arg("top_k"), py::arg("norm_topk"),
+        py::arg("row_tile") = 0);
+  m.def("moe_router_finish", &moe_router_finish);
+  m.def("moe_router_bwd", &moe_router_bwd);
   m.def("lm_head_fwd", &lm_head_fwd, py::arg("h"), py::arg("w"), py::arg("labels"), py::arg("ignore_index"),
         py::arg("ns") = 0);
   m.def("lm_head_dz", &lm_head_dz);

@@ -353,6 +353,21 @@ void launch_moe_combine(const uint16_t* y, const int* slot_row, const float* wts
 void launch_moe_combine_bwd(const uint16_t* y, const int* slot_row, const uint16_t* dout, float* dwts, int64_t T, int k,
                             int D, hipStream_t st);
 
+// ---------------------------------------------------------------- moe_router.hip (fused MoE router)
+// h [T, D], w [E, D] bf16; 1 <= E <= 128, 1 <= k <= min(8, E), D % 64 == 0.  row_tile: 0 (the default: 32), 32, or
+// 64 -- measured slower on every shape and kept for scripts/probe_moe_router.py and one test, never chosen by the op.
+int moe_router_blocks(int T, int row_tile);  // rows of `part` ([blocks, 2 E + 1] fp32: counts | psum | sum lse^2)
+// idx [T, k] int64 (descending logit, a tie to the lower id), wts [T, k], lse [T], logits [T, E] fp32
+void launch_moe_router_fwd(const uint16_t* h, const uint16_t* w, int T, int E, int D, int k, bool norm, int row_tile,
+                           int64_t* idx, float* wts, float* lse, float* logits, float* part, hipStream_t st);
+// counts [E] int32, psum [E], stats [3] = {lb, zl, aux_coef lb + z_coef zl}
+void launch_moe_router_finish(const float* part, int nblk, int T, int E, int k, float aux_coef, float z_coef, int* counts,
+                              float* psum, float* stats, hipStream_t st);
+// dz [T, E] bf16 from the gradients dwts [T, k] and daux (a device scalar)
+void launch_moe_router_bwd(const float* logits, const float* lse, const int64_t* idx, const float* wts, const float* dwts,
+                           const float* daux, const int* counts, int T, int E, int k, bool norm, float aux_coef,
+                           float z_coef, uint16_t* dz, hipStream_t st);
+
 // ---------------------------------------------------------------- lm_head.hip (LM-head loss without the logits)
 // h [T, D], w [V, D] bf16, lab [T] int64; D % 64 == 0, V % 8 == 0.  A scored row: label != ignore and in [0, V).
 // vocabulary splits the forward runs for a request of ns (0: automatic): at most one per 128-column tile, none empty

@@ -37,6 +37,7 @@ ROUTES: Dict[str, str] = {
     "flash_attn": "causal GQA attention on SDPA",
     "fused_xent": "cross-entropy on fp32 logits through F.cross_entropy",
     "moe_ffn": "the mixture-of-experts FFN as the torch loop over experts (ops/moe.py _moe_ref)",
+    "moe_router": "ops.moe.router as the torch composition with logits in the input dtype (ops/moe.py _router_ref)",
     "fused_head": "the LM-head loss as cross_entropy(ps_linear(h, w), labels), logits in memory (ops/lm_head.py)",
     # sparse rows (ops/sparse.py)
     "bag_pool": "multi-hot bags pooled by gather_rows -> weight multiply -> segment_reduce_rows ([nnz, dim] in HBM)",

@@ -25,7 +25,7 @@ from torch.utils.checkpoint import checkpoint
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
 from ..ops.lm_head import linear_cross_entropy
-from ..ops.moe import moe_ffn, route as moe_route
+from ..ops.moe import moe_ffn, route as moe_route, router as moe_router
 from ..ops.transformer import (PackedSeqs, attention_causal_gqa, attention_qkv, cross_entropy,
                               doc_bounds as _doc_bounds, layer_norm_residual, pack_seqs, rms_norm, rope_split,
                               rope_table, swiglu)
@@ -246,6 +246,13 @@ class LlamaConfig:
     moe_top_k: int = 2
     moe_ffn: int = 0
     moe_norm_topk: bool = True
+    # moe_fused_router: routing through ops.moe.router (fp32 logits, a tie to the lower expert id; one GEMM with the
+    # routing in its epilogue on the GPU) instead of ops.moe.route; opt-in: near-tied tokens get other experts.
+    # moe_aux_coef / moe_z_coef: coefficients of the load-balancing loss and the router z-loss that every MoE layer
+    # adds to the loss of ``LlamaForCausalLM.forward(ids, labels)``; non-zero, they select ``router`` too
+    moe_fused_router: bool = False
+    moe_aux_coef: float = 0.0
+    moe_z_coef: float = 0.0
     # with labels, the loss straight from the last hidden states and lm_head.weight, no [B*S, vocab] logits or
     # gradient in memory (ops/lm_head.py); opt-in: it trades time for that memory (profiles/lm_head_probe.txt)
     fused_head: bool = False
@@ -320,11 +327,18 @@ class LlamaBlock(nn.Module):
             self.q_norm = nn.Parameter(torch.ones(hd))
             self.k_norm = nn.Parameter(torch.ones(hd))
 
-    def forward(self, x, r, cs, doc_bounds=None):
+    def forward_aux(self, x, r, cs, doc_bounds=None):
+        """``self(x, r, cs, doc_bounds)`` (through ``__call__``, so module hooks fire as for a plain call) plus the
+        layer's auxiliary router loss: ``c.moe_aux_coef`` * load balancing + ``c.moe_z_coef`` * z-loss, an fp32 zero
+        for a block that has no router loss -> (x, pending, aux), three tensors."""
+        return self(x, r, cs, doc_bounds, with_aux=True)
+
+    def forward(self, x, r, cs, doc_bounds=None, with_aux=False):
         """Residual stream = x + r (r: the previous block's pending MLP output, None for the
         first block) -- the add is fused into this block's first RMSNorm, and this block's
         MLP output is returned pending for the next one.  ``doc_bounds`` (packed rows): the
-        (doc_start, doc_end) pair of ops.transformer.doc_bounds, each token attends inside its document."""
+        (doc_start, doc_end) pair of ops.transformer.doc_bounds, each token attends inside its document.
+        ``with_aux``: the router loss as a third value (``forward_aux``)."""
         b, s, _ = x.shape
         c = self.c
         hd = c.hidden // c.heads
@@ -339,11 +353,20 @@ class LlamaBlock(nn.Module):
             q, k, v = rope_split(qkv, cs, c.heads, c.kv_heads)  # RoPE + split + transpose, one pass
         o = self.wo(attention_causal_gqa(q, k, v, doc_bounds))  # flash kernel (heads merged) or SDPA
         x, h = rms_norm(x, self.mlp_norm.weight, c.eps, residual=o)
-        if c.moe_experts:  # routing in torch on [T, E]; the experts on the grouped kernels (csrc/kernels/moe.hip)
+        aux = None
+        if c.moe_experts:  # routing on [T, E]; the experts on the grouped kernels (csrc/kernels/moe.hip)
             hf = h.reshape(b * s, c.hidden)
-            idx, wts = moe_route(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk)
-            return x, moe_ffn(hf, idx, wts, self.w13_e, self.w2_e).view(b, s, c.hidden)
-        return x, self.w2(swiglu(self.w13(h)))
+            if c.moe_fused_router or c.moe_aux_coef or c.moe_z_coef:  # csrc/kernels/moe_router.hip
+                idx, wts, aux = moe_router(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk, c.moe_aux_coef,
+                                           c.moe_z_coef)
+            else:  # in torch
+                idx, wts = moe_route(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk)
+            out = moe_ffn(hf, idx, wts, self.w13_e, self.w2_e).view(b, s, c.hidden)
+        else:
+            out = self.w2(swiglu(self.w13(h)))
+        if not with_aux:
+            return x, out
+        return x, out, torch.zeros((), dtype=torch.float32, device=x.device) if aux is None else aux
 
 
 class LlamaForCausalLM(nn.Module):
@@ -351,6 +374,7 @@ class LlamaForCausalLM(nn.Module):
         super().__init__()
         self.c = c
         self.checkpointing = checkpointing
+        self.last_aux = []  # the last loss's per-layer router losses, detached (for logging)
         self.embed = nn.Embedding(c.vocab, c.hidden)
         self.layers = nn.ModuleList(LlamaBlock(c) for _ in range(c.layers))
         self.norm = RMSNorm(c.hidden, c.eps)
@@ -374,11 +398,17 @@ class LlamaForCausalLM(nn.Module):
                 raise ValueError("doc_ids: [B, S] like ids")
             bounds = _doc_bounds(doc_ids)
         x, r = self.embed(ids), None
+        # the layers' router losses (moe_aux_coef / moe_z_coef) join the loss; detached per layer in self.last_aux
+        with_aux = bool(self.c.moe_experts and labels is not None and (self.c.moe_aux_coef or self.c.moe_z_coef))
+        auxes = []
         for layer in self.layers:
+            fn = layer.forward_aux if with_aux else layer
             if self.checkpointing and self.training:
-                x, r = checkpoint(layer, x, r, cs, bounds, use_reentrant=False)
+                out = checkpoint(fn, x, r, cs, bounds, use_reentrant=False)
             else:
-                x, r = layer(x, r, cs, bounds)
+                out = fn(x, r, cs, bounds)
+            x, r = out[:2]
+            auxes.extend(out[2:])
         _, h = rms_norm(x, self.norm.weight, self.c.eps, residual=r)
         if labels is None:
             return self.lm_head(h)
@@ -387,8 +417,13 @@ class LlamaForCausalLM(nn.Module):
         if doc_ids is not None:  # nor has a document's last position
             tgt[:, :-1].masked_fill_(doc_ids[:, 1:] != doc_ids[:, :-1], -100)
         if self.c.fused_head:
-            return linear_cross_entropy(h, self.lm_head.weight, tgt, ignore_index=-100)
-        return cross_entropy(self.lm_head(h), tgt, ignore_index=-100)
+            loss = linear_cross_entropy(h, self.lm_head.weight, tgt, ignore_index=-100)
+        else:
+            loss = cross_entropy(self.lm_head(h), tgt, ignore_index=-100)
+        if with_aux:
+            self.last_aux = [a.detach() for a in auxes]
+            loss = loss + torch.stack(auxes).sum().to(loss.dtype)
+        return loss
 
 
 def packed_lm_batch(batch: int, seq: int, vocab: int, doc_lengths, seed: int = 0, device=None):

@@ -3,8 +3,9 @@
   moe_ffn(x, idx, wts, w13, w2) -> out[t] = sum_j wts[t, j] * (swiglu(x[t] @ w13[idx[t, j]].T) @ w2[idx[t, j]].T)
 
 ``x`` [T, D] bf16, ``idx`` [T, k] integer expert ids in [0, E) (the k ids of a token distinct), ``wts`` [T, k] fp32,
-``w13`` [E, 2F, D] (gate rows, then up rows, as ``LlamaBlock.w13``), ``w2`` [E, D, F].  Routing (router logits,
-softmax, topk, renormalisation and their autograd) stays outside, in torch.
+``w13`` [E, 2F, D] (gate rows, then up rows, as ``LlamaBlock.w13``), ``w2`` [E, D, F].  Routing stays outside:
+``route`` (router logits, softmax, topk, renormalisation and their autograd in torch, bf16 logits) or ``router``
+(one GEMM with the routing in its epilogue, fp32 logits, plus the load-balancing and z losses).
 
 The fused route: ``moe_plan`` sorts the T * k (token, slot) pairs by expert into a row space in which every
 expert's segment starts at a multiple of the 128-row GEMM tile (R_cap rows, sized from T, k and E alone: no host
@@ -19,7 +20,7 @@ PS_AMD_DISABLE=moe_ffn the op is ``_moe_ref``, the torch composition.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -128,3 +129,87 @@ def route(h: torch.Tensor, router_weight: torch.Tensor, top_k: int, norm_topk: b
     if norm_topk:
         wts = wts / wts.sum(-1, keepdim=True)
     return idx, wts
+
+
+# ----------------------------------------------------------------------------------- fused router (moe_router.hip)
+def _router_ref(h: torch.Tensor, w: torch.Tensor, top_k: int, norm_topk: bool = True, aux_coef: float = 0.0,
+                z_coef: float = 0.0, idx: Optional[torch.Tensor] = None):
+    """The definition of ``router`` as a torch composition in the dtype of its inputs (bf16 inputs: the logits are a
+    bf16 matmul output, as in ``route``; fp64 inputs: the high-precision reference).  ``idx`` overrides the top-k
+    choice.  No host sync.  -> (idx, wts, aux)"""
+    z = F.linear(h, w)
+    z = z.to(torch.promote_types(z.dtype, torch.float32))
+    lse = torch.logsumexp(z, -1)
+    p = (z - lse[:, None]).exp()
+    if idx is None:  # descending, a tie to the lower id
+        idx = torch.sort(z, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    wts = p.gather(1, idx)
+    if norm_topk:
+        wts = wts / wts.sum(-1, keepdim=True)
+    E = w.shape[0]
+    flat = idx.reshape(-1)
+    counts = torch.zeros(E, dtype=torch.int64, device=z.device).scatter_add_(0, flat, torch.ones_like(flat))
+    lb = E * ((counts.to(z.dtype) / flat.numel()) * p.mean(0)).sum()  # f carries no gradient, P does
+    zl = (lse * lse).mean()
+    return idx, wts, aux_coef * lb + z_coef * zl
+
+
+def router_ok(h: torch.Tensor, w: torch.Tensor, top_k: int) -> bool:
+    """The fused router's domain.  The kernel reads 16 B at a time: a contiguous view that does not start on a 16-byte
+    boundary takes the composition (a non-contiguous tensor is copied, and the copy is aligned)."""
+    if not (h.is_cuda and w.is_cuda and h.device == w.device):
+        return False
+    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (h, w)):
+        return False
+    return (h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and h.shape[0] >= 1
+            and h.shape[1] % 64 == 0 and h.shape[1] >= 64 and 1 <= w.shape[0] <= MAX_EXPERTS
+            and 1 <= top_k <= min(MAX_TOP_K, w.shape[0]) and knobs.enabled("moe_router"))
+
+
+class _Router(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w, top_k, norm_topk, aux_coef, z_coef):
+        """h [T, D], w [E, D] bf16 -> (idx, wts, aux, counts [E] int32)"""
+        n = native()
+        h, w = h.contiguous(), w.contiguous()
+        idx, wts, lse, logits, part = n.moe_router_fwd(h, w, top_k, norm_topk)
+        counts, _, stats = n.moe_router_finish(part, h.shape[0], top_k, aux_coef, z_coef)
+        ctx.save_for_backward(h, w, logits, lse, idx, wts, counts)
+        ctx.args = (norm_topk, aux_coef, z_coef)
+        ctx.mark_non_differentiable(idx, counts)
+        return idx, wts, stats[2], counts
+
+    @staticmethod
+    def backward(ctx, _didx, dwts, daux, _dcounts):
+        h, w, logits, lse, idx, wts, counts = ctx.saved_tensors
+        dwts = torch.zeros_like(wts) if dwts is None else dwts.float().contiguous()
+        daux = lse.new_zeros(1) if daux is None else daux.float().reshape(1)
+        dz = native().moe_router_bwd(logits, lse, idx, wts, dwts, daux, counts, *ctx.args)  # [T, E] bf16
+        dh = torch.mm(dz, w) if ctx.needs_input_grad[0] else None
+        dw = torch.mm(dz.t(), h) if ctx.needs_input_grad[1] else None
+        return dh, dw, None, None, None, None
+
+
+def router(h: torch.Tensor, router_weight: torch.Tensor, top_k: int, norm_topk: bool = True, aux_coef: float = 0.0,
+           z_coef: float = 0.0):
+    """Router with fp32 logits and the auxiliary losses.  ``h`` [T, D], ``router_weight`` [E, D] ->
+    (idx [T, k] int64: the k experts of largest logit, descending, a tie to the lower id; wts [T, k]: their softmax
+    probabilities, renormalised over the k when ``norm_topk``; aux: ``aux_coef`` * load-balancing loss (Switch /
+    Mixtral: E sum_e f_e P_e) + ``z_coef`` * router z-loss (mean lse^2)).  Gradients to ``h`` and ``router_weight``
+    from ``wts`` and ``aux``; no host sync.  On ``router_ok`` one MFMA GEMM with the routing in its epilogue
+    (csrc/kernels/moe_router.hip), the logits never rounded below fp32; otherwise, and under
+    PS_AMD_DISABLE=moe_router, ``_router_ref``.  ``router.last_counts`` holds the per-expert pair counts [E] int32 of
+    the most recent fused call only: every call overwrites it, so with several MoE layers it is the last layer's, and
+    a recomputation under activation checkpointing writes it again.  Read it right after the call it belongs to."""
+    if h.dim() != 2 or router_weight.dim() != 2 or h.shape[1] != router_weight.shape[1]:
+        raise ValueError("router: h [T, D], router_weight [E, D]")
+    if not 1 <= top_k <= router_weight.shape[0]:
+        raise ValueError("router: 1 <= top_k <= E")
+    if not router_ok(h, router_weight, top_k):
+        return _router_ref(h, router_weight, top_k, norm_topk, aux_coef, z_coef)
+    idx, wts, aux, router.last_counts = _Router.apply(h, router_weight, int(top_k), bool(norm_topk), float(aux_coef),
+                                                      float(z_coef))
+    return idx, wts, aux
+
+
+router.last_counts = None
