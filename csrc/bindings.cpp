@@ -1490,8 +1490,10 @@ Tensor moe_combine_bwd(Tensor y, std::vector<Tensor> plan, Tensor dout) {
 
 // ------------------------------------------------------------------------------ fused MoE router (moe_router.hip)
 // h [T, D], w [E, D] bf16 -> {idx [T, k] int64, wts [T, k], lse [T], logits [T, E], part [blocks, 2 E + 1]} (fp32);
-// row_tile: 0 (automatic), 32 or 64
-std::vector<Tensor> moe_router_fwd(Tensor h, Tensor w, int64_t k, bool norm_topk, int64_t row_tile) {
+// row_tile: 0 (automatic), 32 or 64.  sigmoid: scores sigmoid(z), selection on score + bias (bias [E] fp32 or none)
+// inside the topk_group best of n_group expert groups, wts times scale; part's psum columns then sum s / sum_e s.
+std::vector<Tensor> moe_router_fwd(Tensor h, Tensor w, int64_t k, bool norm_topk, int64_t row_tile, bool sigmoid,
+                                   c10::optional<Tensor> bias, int64_t n_group, int64_t topk_group, double scale) {
   check_rows(h, "h");
   check_rows(w, "w");
   TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && h.size(1) == w.size(1), "moe_router_fwd: h [T, D], w [E, D]");
@@ -1502,6 +1504,21 @@ std::vector<Tensor> moe_router_fwd(Tensor h, Tensor w, int64_t k, bool norm_topk
   TORCH_CHECK(T >= 1 && T < (int64_t(1) << 31) - 64, "moe_router_fwd: 1 <= T < 2^31");
   TORCH_CHECK(row_tile == 0 || row_tile == 32 || row_tile == 64, "moe_router_fwd: row_tile 0, 32 or 64");
   TORCH_CHECK(al16(h.data_ptr()) && al16(w.data_ptr()), "moe_router_fwd: 16-byte aligned");
+  const float* bias_p = nullptr;
+  if (sigmoid) {
+    TORCH_CHECK(row_tile != 64, "moe_router_fwd: the sigmoid epilogue has the 32-row tile only");
+    TORCH_CHECK(topk_group >= 1 && topk_group <= n_group && n_group <= 32 && E % n_group == 0,
+                "moe_router_fwd: E % n_group == 0, 1 <= topk_group <= n_group <= 32, got ", n_group, ", ", topk_group);
+    TORCH_CHECK(k <= topk_group * (E / n_group), "moe_router_fwd: k <= topk_group * E / n_group, got ", k);
+    if (bias.has_value()) {
+      check_f32(*bias, "bias");
+      TORCH_CHECK(bias->dim() == 1 && bias->size(0) == E && bias->device() == h.device(), "moe_router_fwd: bias [E] beside h");
+      bias_p = bias->data_ptr<float>();
+    }
+  } else {
+    TORCH_CHECK(!bias.has_value() && n_group == 1 && topk_group == 1 && scale == 1.0,
+                "moe_router_fwd: bias, groups and scale belong to the sigmoid scores");
+  }
   const c10::DeviceGuard guard(h.device());
   auto fopt = h.options().dtype(torch::kFloat32);
   const int rt = static_cast<int>(row_tile), blocks = psamd::moe_router_blocks(static_cast<int>(T), rt);
@@ -1509,7 +1526,9 @@ std::vector<Tensor> moe_router_fwd(Tensor h, Tensor w, int64_t k, bool norm_topk
   auto lse = torch::empty({T}, fopt), logits = torch::empty({T, E}, fopt), part = torch::empty({blocks, 2 * E + 1}, fopt);
   psamd::launch_moe_router_fwd(u16(h), u16(w), static_cast<int>(T), static_cast<int>(E), static_cast<int>(D),
                                static_cast<int>(k), norm_topk, rt, idx.data_ptr<int64_t>(), wts.data_ptr<float>(),
-                               lse.data_ptr<float>(), logits.data_ptr<float>(), part.data_ptr<float>(), cur_stream(h));
+                               lse.data_ptr<float>(), logits.data_ptr<float>(), part.data_ptr<float>(), sigmoid, bias_p,
+                               static_cast<int>(n_group), static_cast<int>(topk_group), static_cast<float>(scale),
+                               cur_stream(h));
   return {idx, wts, lse, logits, part};
 }
 
@@ -1531,9 +1550,9 @@ std::vector<Tensor> moe_router_finish(Tensor part, int64_t T, int64_t k, double 
   return {counts, psum, stats};
 }
 
-// dz [T, E] bf16: the gradient of the logits from dwts [T, k] and daux (one element)
+// dz [T, E] bf16: the gradient of the logits from dwts [T, k] and daux (one element); sigmoid, scale: the forward's
 Tensor moe_router_bwd(Tensor logits, Tensor lse, Tensor idx, Tensor wts, Tensor dwts, Tensor daux, Tensor counts,
-                      bool norm_topk, double aux_coef, double z_coef) {
+                      bool norm_topk, double aux_coef, double z_coef, bool sigmoid, double scale) {
   check_f32(logits, "logits");
   check_f32(lse, "lse");
   check_f32(wts, "wts");
@@ -1554,7 +1573,8 @@ Tensor moe_router_bwd(Tensor logits, Tensor lse, Tensor idx, Tensor wts, Tensor 
   psamd::launch_moe_router_bwd(logits.data_ptr<float>(), lse.data_ptr<float>(), idx.data_ptr<int64_t>(),
                                wts.data_ptr<float>(), dwts.data_ptr<float>(), daux.data_ptr<float>(), i32(counts),
                                static_cast<int>(T), static_cast<int>(E), static_cast<int>(k), norm_topk,
-                               static_cast<float>(aux_coef), static_cast<float>(z_coef), u16m(dz), cur_stream(logits));
+                               static_cast<float>(aux_coef), static_cast<float>(z_coef), sigmoid,
+                               static_cast<float>(scale), u16m(dz), cur_stream(logits));
   return dz;
 }
 
@@ -2656,9 +2676,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine", &moe_combine);
   m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("moe_router_fwd", &moe_router_fwd, py::arg("h"), py::arg("w"), py::arg("top_k"), py::arg("norm_topk"),
-        py::arg("row_tile") = 0);
+        py::arg("row_tile") = 0, py::arg("sigmoid") = false, py::arg("bias") = py::none(), py::arg("n_group") = 1,
+        py::arg("topk_group") = 1, py::arg("scale") = 1.0);
   m.def("moe_router_finish", &moe_router_finish);
-  m.def("moe_router_bwd", &moe_router_bwd);
+  m.def("moe_router_bwd", &moe_router_bwd, py::arg("logits"), py::arg("lse"), py::arg("idx"), py::arg("wts"),
+        py::arg("dwts"), py::arg("daux"), py::arg("counts"), py::arg("norm_topk"), py::arg("aux_coef"),
+        py::arg("z_coef"), py::arg("sigmoid") = false, py::arg("scale") = 1.0);
   m.def("lm_head_fwd", &lm_head_fwd, py::arg("h"), py::arg("w"), py::arg("labels"), py::arg("ignore_index"),
         py::arg("ns") = 0);
   m.def("lm_head_dz", &lm_head_dz);

@@ -357,16 +357,21 @@ void launch_moe_combine_bwd(const uint16_t* y, const int* slot_row, const uint16
 // h [T, D], w [E, D] bf16; 1 <= E <= 128, 1 <= k <= min(8, E), D % 64 == 0.  row_tile: 0 (the default: 32), 32, or
 // 64 -- measured slower on every shape and kept for scripts/probe_moe_router.py and one test, never chosen by the op.
 int moe_router_blocks(int T, int row_tile);  // rows of `part` ([blocks, 2 E + 1] fp32: counts | psum | sum lse^2)
-// idx [T, k] int64 (descending logit, a tie to the lower id), wts [T, k], lse [T], logits [T, E] fp32
+// idx [T, k] int64 (descending logit, a tie to the lower id), wts [T, k], lse [T], logits [T, E] fp32.
+// sigmoid: scores sigmoid(z), chosen on score + bias (bias [E] fp32 or null) among the topk_group best of n_group
+// groups of E / n_group consecutive experts (E % n_group == 0, 1 <= topk_group <= n_group <= 32,
+// k <= topk_group E / n_group; n_group == topk_group: no group limit), wts times scale, psum over s / sum_e s;
+// row_tile 0 or 32.  Without it bias is null, n_group = topk_group = 1 and scale = 1.
 void launch_moe_router_fwd(const uint16_t* h, const uint16_t* w, int T, int E, int D, int k, bool norm, int row_tile,
-                           int64_t* idx, float* wts, float* lse, float* logits, float* part, hipStream_t st);
+                           int64_t* idx, float* wts, float* lse, float* logits, float* part, bool sigmoid,
+                           const float* bias, int n_group, int topk_group, float scale, hipStream_t st);
 // counts [E] int32, psum [E], stats [3] = {lb, zl, aux_coef lb + z_coef zl}
 void launch_moe_router_finish(const float* part, int nblk, int T, int E, int k, float aux_coef, float z_coef, int* counts,
                               float* psum, float* stats, hipStream_t st);
-// dz [T, E] bf16 from the gradients dwts [T, k] and daux (a device scalar)
+// dz [T, E] bf16 from the gradients dwts [T, k] and daux (a device scalar); sigmoid / scale as in the forward
 void launch_moe_router_bwd(const float* logits, const float* lse, const int64_t* idx, const float* wts, const float* dwts,
                            const float* daux, const int* counts, int T, int E, int k, bool norm, float aux_coef,
-                           float z_coef, uint16_t* dz, hipStream_t st);
+                           float z_coef, bool sigmoid, float scale, uint16_t* dz, hipStream_t st);
 
 // ---------------------------------------------------------------- lm_head.hip (LM-head loss without the logits)
 // h [T, D], w [V, D] bf16, lab [T] int64; D % 64 == 0, V % 8 == 0.  A scored row: label != ignore and in [0, V).

@@ -12,6 +12,10 @@
 //   moe_router_bwd     one wave per row: dz = p (g - <p, g>) + daux z_coef (2 lse / T) p, where g holds the top-k
 //                      weights' gradient on the chosen columns (through the renormalisation when it was applied)
 //                      plus daux aux_coef E f_e / T on every column; one rounding to bf16.
+//   sigmoid form       (DeepSeek-V3 style) the forward's SIG epilogue and moe_router_sigmoid_bwd: scores sigmoid(z), the
+//                      k experts of largest score + bias inside the topk_group best of n_group expert groups (group
+//                      score: its two largest score + bias summed), weights the unbiased scores (renormalised when
+//                      asked) times a scale; psum sums score / row sum of scores.  Same partial rows, same finish.
 //
 // Forward design.  The problem streams h once from HBM; Wr (at most 1 MB) stays in every XCD's L2, so the block
 // order is the plain walk along the rows.  A block owns TM token rows (32 or 64) and ALL columns, padded inside the
@@ -56,6 +60,7 @@ __device__ __forceinline__ uint32_t ordered_bits(float z) {
 __device__ __forceinline__ float from_ordered_bits(uint32_t o) {
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
+__device__ __forceinline__ float sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -77,12 +82,15 @@ struct RouterTile {
 };
 
 // ------------------------------------------------------------------------------------------ forward
-template <int TM, int NB>
+// SIG: the sigmoid epilogue (scores sigmoid(z), selection on score + bias, group-limited, weights times `scale`);
+// the softmax instantiations read none of bias, n_group, topk_group and scale.
+template <int TM, int NB, bool SIG>
 __global__ __launch_bounds__(kNT) void moe_router_fwd_kernel(const uint16_t* __restrict__ h, const uint16_t* __restrict__ w,
                                                              int T, int E, int D, int k, int norm,
                                                              int64_t* __restrict__ idx, float* __restrict__ wts,
                                                              float* __restrict__ lse, float* __restrict__ logits,
-                                                             float* __restrict__ part) {
+                                                             float* __restrict__ part, const float* __restrict__ bias,
+                                                             int n_group, int topk_group, float scale) {
   using RT = RouterTile<TM, NB>;
   constexpr int MB = RT::MB, LD = RT::LD, kA = RT::kA, kB = RT::kB;
   __shared__ __attribute__((aligned(16))) unsigned char raw[RT::kBytes];  // As[2] | Bs[2]; then the fp32 tile
@@ -183,47 +191,127 @@ __global__ __launch_bounds__(kNT) void moe_router_fwd_kernel(const uint16_t* __r
   // rows wave, wave + 4, ...: a lane holds columns lane and lane + 64
   const bool v0 = lane < E, v1 = lane + 64 < E;
   float cnt0 = 0.f, cnt1 = 0.f, ps0 = 0.f, ps1 = 0.f, zsq = 0.f;
-  for (int r = wave; r < TM; r += 4) {
-    const int t = r0 + r;
-    if (t >= T) break;  // wave-uniform
-    const float z0 = v0 ? L[r * LD + lane] : -INFINITY, z1 = v1 ? L[r * LD + lane + 64] : -INFINITY;
-    const float m = wave_max(fmaxf(z0, z1));
-    const float s = wave_sum((v0 ? expf(z0 - m) : 0.f) + (v1 ? expf(z1 - m) : 0.f));
-    const float l = m + logf(s);
-    const float p0 = v0 ? expf(z0 - l) : 0.f, p1 = v1 ? expf(z1 - l) : 0.f;
-    // a retired or pad column: key 0, below every live key (ordered bits of a live column >= 0x007fffff)
-    unsigned long long key0 = v0 ? (static_cast<unsigned long long>(ordered_bits(z0)) << 32) | static_cast<uint32_t>(~lane) : 0ull;
-    unsigned long long key1 = v1 ? (static_cast<unsigned long long>(ordered_bits(z1)) << 32) | static_cast<uint32_t>(~(lane + 64)) : 0ull;
-    int my_e = 0;
-    float my_p = 0.f, sel = 0.f;
-    for (int j = 0; j < k; ++j) {
-      const unsigned long long best = wave_max_u64(key0 > key1 ? key0 : key1);
-      const int e = static_cast<int>(~static_cast<uint32_t>(best)) & 127;
-      const float pe = expf(from_ordered_bits(static_cast<uint32_t>(best >> 32)) - l);  // the owner's p, bit for bit
-      if (lane == j) {
-        my_e = e;
-        my_p = pe;
+  if constexpr (SIG) {
+    const int G = E / n_group;                 // a group: G consecutive columns
+    const bool grouped = n_group > topk_group;  // otherwise every group is kept: no group step
+    const float bi0 = v0 && bias ? bias[lane] : 0.f, bi1 = v1 && bias ? bias[lane + 64] : 0.f;
+    const int grp0 = lane / G, grp1 = (lane + 64) / G;
+    for (int r = wave; r < TM; r += 4) {
+      const int t = r0 + r;
+      if (t >= T) break;  // wave-uniform
+      float* Lr = L + r * LD;
+      const float z0 = v0 ? Lr[lane] : -INFINITY, z1 = v1 ? Lr[lane + 64] : -INFINITY;
+      const float m = wave_max(fmaxf(z0, z1));
+      const float l = m + logf(wave_sum((v0 ? expf(z0 - m) : 0.f) + (v1 ? expf(z1 - m) : 0.f)));
+      const float s0 = v0 ? sigmoid(z0) : 0.f, s1 = v1 ? sigmoid(z1) : 0.f;
+      const float ssum = wave_sum(s0 + s1);
+      const float c0 = s0 + bi0, c1 = s1 + bi1;  // the selection scores
+      unsigned long long key0 = v0 ? (static_cast<unsigned long long>(ordered_bits(c0)) << 32) | static_cast<uint32_t>(~lane) : 0ull;
+      unsigned long long key1 = v1 ? (static_cast<unsigned long long>(ordered_bits(c1)) << 32) | static_cast<uint32_t>(~(lane + 64)) : 0ull;
+      if (grouped) {  // block-uniform
+        // The row of the tile is this wave's alone and its logits are in registers: it takes the selection scores,
+        // and lane g < n_group walks group g's run of them (any G, a run may straddle the lane / lane + 64 split)
+        // for the two largest.  A wave's LDS operations complete in order: the walk sees the row's stores.
+        if (v0) Lr[lane] = c0;
+        if (v1) Lr[lane + 64] = c1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        unsigned long long gkey = 0ull;
+        if (lane < n_group) {
+          const float* cg = Lr + lane * G;  // columns lane G .. lane G + G - 1 < E
+          float m1 = -INFINITY, m2 = -INFINITY;  // a NaN enters neither
+#pragma unroll 4
+          for (int i = 0; i < G; ++i) {
+            const float c = cg[i];
+            m2 = c > m1 ? m1 : (c > m2 ? c : m2);
+            m1 = c > m1 ? c : m1;
+          }
+          gkey = (static_cast<unsigned long long>(ordered_bits(G > 1 ? m1 + m2 : m1)) << 32) | static_cast<uint32_t>(~lane);
+        }
+        uint32_t keep = 0u;  // bit g: group g is among the topk_group of largest score, a tie to the lower id
+        for (int j = 0; j < topk_group; ++j) {
+          const unsigned long long best = wave_max_u64(gkey);
+          keep |= 1u << (~static_cast<uint32_t>(best) & 31u);
+          if (gkey == best) gkey = 0ull;
+        }
+        if (v0 && !((keep >> grp0) & 1u)) key0 = 0ull;  // a dropped group's columns: key 0, like pad columns
+        if (v1 && !((keep >> grp1) & 1u)) key1 = 0ull;
       }
-      sel += pe;  // j ascending, on every lane
-      if (key0 == best) {
-        key0 = 0ull;
-        cnt0 += 1.f;
+      int my_e = 0;
+      float my_s = 0.f, sel = 0.f;
+      for (int j = 0; j < k; ++j) {
+        const unsigned long long best = wave_max_u64(key0 > key1 ? key0 : key1);
+        const int e = static_cast<int>(~static_cast<uint32_t>(best)) & 127;
+        const float se = __shfl((e >> 6) ? s1 : s0, e & 63, kWave);  // the unbiased score, from its owner
+        if (lane == j) {
+          my_e = e;
+          my_s = se;
+        }
+        sel += se;  // j ascending, on every lane
+        if (key0 == best) {
+          key0 = 0ull;
+          cnt0 += 1.f;
+        }
+        if (key1 == best) {
+          key1 = 0ull;
+          cnt1 += 1.f;
+        }
       }
-      if (key1 == best) {
-        key1 = 0ull;
-        cnt1 += 1.f;
+      if (lane < k) {
+        idx[static_cast<int64_t>(t) * k + lane] = my_e;
+        wts[static_cast<int64_t>(t) * k + lane] = (norm ? my_s / sel : my_s) * scale;
       }
+      if (lane == 0) lse[t] = l;
+      if (v0) logits[static_cast<int64_t>(t) * E + lane] = z0;
+      if (v1) logits[static_cast<int64_t>(t) * E + lane + 64] = z1;
+      ps0 += s0 / ssum;  // DeepSeek-V3's normalised scores take the probabilities' place in the balance loss
+      ps1 += s1 / ssum;
+      zsq += l * l;
     }
-    if (lane < k) {
-      idx[static_cast<int64_t>(t) * k + lane] = my_e;
-      wts[static_cast<int64_t>(t) * k + lane] = norm ? my_p / sel : my_p;
+  } else {
+    for (int r = wave; r < TM; r += 4) {
+      const int t = r0 + r;
+      if (t >= T) break;  // wave-uniform
+      const float z0 = v0 ? L[r * LD + lane] : -INFINITY, z1 = v1 ? L[r * LD + lane + 64] : -INFINITY;
+      const float m = wave_max(fmaxf(z0, z1));
+      const float s = wave_sum((v0 ? expf(z0 - m) : 0.f) + (v1 ? expf(z1 - m) : 0.f));
+      const float l = m + logf(s);
+      const float p0 = v0 ? expf(z0 - l) : 0.f, p1 = v1 ? expf(z1 - l) : 0.f;
+      // a retired or pad column: key 0, below every live key (ordered bits of a live column >= 0x007fffff)
+      unsigned long long key0 = v0 ? (static_cast<unsigned long long>(ordered_bits(z0)) << 32) | static_cast<uint32_t>(~lane) : 0ull;
+      unsigned long long key1 = v1 ? (static_cast<unsigned long long>(ordered_bits(z1)) << 32) | static_cast<uint32_t>(~(lane + 64)) : 0ull;
+      int my_e = 0;
+      float my_p = 0.f, sel = 0.f;
+      for (int j = 0; j < k; ++j) {
+        const unsigned long long best = wave_max_u64(key0 > key1 ? key0 : key1);
+        const int e = static_cast<int>(~static_cast<uint32_t>(best)) & 127;
+        const float pe = expf(from_ordered_bits(static_cast<uint32_t>(best >> 32)) - l);  // the owner's p, bit for bit
+        if (lane == j) {
+          my_e = e;
+          my_p = pe;
+        }
+        sel += pe;  // j ascending, on every lane
+        if (key0 == best) {
+          key0 = 0ull;
+          cnt0 += 1.f;
+        }
+        if (key1 == best) {
+          key1 = 0ull;
+          cnt1 += 1.f;
+        }
+      }
+      if (lane < k) {
+        idx[static_cast<int64_t>(t) * k + lane] = my_e;
+        wts[static_cast<int64_t>(t) * k + lane] = norm ? my_p / sel : my_p;
+      }
+      if (lane == 0) lse[t] = l;
+      if (v0) logits[static_cast<int64_t>(t) * E + lane] = z0;
+      if (v1) logits[static_cast<int64_t>(t) * E + lane + 64] = z1;
+      ps0 += p0;
+      ps1 += p1;
+      zsq += l * l;
     }
-    if (lane == 0) lse[t] = l;
-    if (v0) logits[static_cast<int64_t>(t) * E + lane] = z0;
-    if (v1) logits[static_cast<int64_t>(t) * E + lane + 64] = z1;
-    ps0 += p0;
-    ps1 += p1;
-    zsq += l * l;
   }
   __syncthreads();  // the tile is read: the waves' partials go on top of it
 
@@ -346,6 +434,60 @@ __global__ __launch_bounds__(kNT) void moe_router_bwd_kernel(const float* __rest
   }
 }
 
+// The sigmoid form, one wave per row.  s = sigmoid(z), S = sum_e s_e, n = s / S and p = softmax(z) are recomputed
+// from the saved logits and lse; g_j, the gradient of s on the chosen slot j, is dwts_j scale (through the
+// renormalisation: (dwts_j scale - <dwts, wts>) / sum s_sel); b_e = daux aux_coef E f_e / T acts through n:
+// ds_e = g_e + (b_e - <n, b>) / S, dz_e = ds_e s_e (1 - s_e) + daux z_coef (2 lse / T) p_e; one rounding to bf16.
+__global__ __launch_bounds__(kNT) void moe_router_sigmoid_bwd_kernel(
+    const float* __restrict__ logits, const float* __restrict__ lse, const int64_t* __restrict__ idx,
+    const float* __restrict__ wts, const float* __restrict__ dwts, const float* __restrict__ daux,
+    const int* __restrict__ counts, int T, int E, int k, int norm, float aux_coef, float z_coef, float scale,
+    uint16_t* __restrict__ dz) {
+  const int lane = threadIdx.x & 63;
+  const bool v0 = lane < E, v1 = lane + 64 < E;
+  const float da = daux[0], fT = static_cast<float>(T);
+  const float bal = da * aux_coef * static_cast<float>(E) / (fT * static_cast<float>(k)) / fT;
+  const float b0 = v0 ? bal * static_cast<float>(counts[lane]) : 0.f;
+  const float b1 = v1 ? bal * static_cast<float>(counts[lane + 64]) : 0.f;
+  const float zc = da * z_coef * 2.f / fT;
+  const int64_t nw = static_cast<int64_t>(gridDim.x) * (kNT / 64);
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * (kNT / 64) + (threadIdx.x >> 6); t < T; t += nw) {
+    const float* zr = logits + t * E;
+    const float l = lse[t];
+    const float z0 = v0 ? zr[lane] : 0.f, z1 = v1 ? zr[lane + 64] : 0.f;
+    const float p0 = v0 ? expf(z0 - l) : 0.f, p1 = v1 ? expf(z1 - l) : 0.f;
+    const float s0 = v0 ? sigmoid(z0) : 0.f, s1 = v1 ? sigmoid(z1) : 0.f;
+    const float ssum = wave_sum(s0 + s1);
+    int e = -1;  // lane j < k: slot j of the row
+    float dw = 0.f, wj = 0.f, sj = 0.f;
+    if (lane < k) {
+      const int64_t ev = idx[t * k + lane];
+      e = (ev >= 0 && ev < E) ? static_cast<int>(ev) : -1;  // an id off [0, E) never becomes an index
+      dw = dwts[t * k + lane];
+      wj = wts[t * k + lane];
+      if (e >= 0) sj = sigmoid(zr[e]);
+    }
+    float gs = dw * scale;
+    if (norm) {  // wts = scale s_sel / sum s_sel
+      const float dot = wave_sum(dw * wj), sel = wave_sum(sj);
+      gs = (dw * scale - dot) / sel;
+    }
+    float g0 = 0.f, g1 = 0.f;
+    for (int j = 0; j < k; ++j) {
+      const int ej = __shfl(e, j, kWave);
+      const float gj = __shfl(gs, j, kWave);
+      if (ej >= 0 && lane == (ej & 63)) {
+        if (ej >> 6) g1 += gj;
+        else g0 += gj;
+      }
+    }
+    const float nb = wave_sum(s0 * b0 + s1 * b1) / ssum;  // <n, b>
+    const float ds0 = g0 + (b0 - nb) / ssum, ds1 = g1 + (b1 - nb) / ssum;
+    if (v0) dz[t * E + lane] = f32_to_bf16(ds0 * s0 * (1.f - s0) + zc * l * p0);
+    if (v1) dz[t * E + lane + 64] = f32_to_bf16(ds1 * s1 * (1.f - s1) + zc * l * p1);
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ launches
@@ -360,23 +502,26 @@ int moe_router_blocks(int T, int row_tile) {
 }
 
 void launch_moe_router_fwd(const uint16_t* h, const uint16_t* w, int T, int E, int D, int k, bool norm, int row_tile,
-                           int64_t* idx, float* wts, float* lse, float* logits, float* part, hipStream_t st) {
+                           int64_t* idx, float* wts, float* lse, float* logits, float* part, bool sigmoid,
+                           const float* bias, int n_group, int topk_group, float scale, hipStream_t st) {
   const int tm = router_row_tile(row_tile), nb = (E + 31) / 32;
   const dim3 grid(moe_router_blocks(T, row_tile)), block(kNT);
-#define PSAMD_ROUTER(TMV, NBV)                                                                                     \
-  hipLaunchKernelGGL((moe_router_fwd_kernel<TMV, NBV>), grid, block, 0, st, h, w, T, E, D, k, norm ? 1 : 0, idx, wts, \
-                     lse, logits, part)
-#define PSAMD_ROUTER_NB(TMV)          \
-  switch (nb) {                       \
-    case 1: PSAMD_ROUTER(TMV, 1); break; \
-    case 2: PSAMD_ROUTER(TMV, 2); break; \
-    case 3: PSAMD_ROUTER(TMV, 3); break; \
-    default: PSAMD_ROUTER(TMV, 4); break; \
+#define PSAMD_ROUTER(TMV, NBV, SIGV)                                                                               \
+  hipLaunchKernelGGL((moe_router_fwd_kernel<TMV, NBV, SIGV>), grid, block, 0, st, h, w, T, E, D, k, norm ? 1 : 0, idx, \
+                     wts, lse, logits, part, bias, n_group, topk_group, scale)
+#define PSAMD_ROUTER_NB(TMV, SIGV)             \
+  switch (nb) {                                \
+    case 1: PSAMD_ROUTER(TMV, 1, SIGV); break; \
+    case 2: PSAMD_ROUTER(TMV, 2, SIGV); break; \
+    case 3: PSAMD_ROUTER(TMV, 3, SIGV); break; \
+    default: PSAMD_ROUTER(TMV, 4, SIGV); break; \
   }
-  if (tm == 64) {
-    PSAMD_ROUTER_NB(64)
+  if (sigmoid) {  // the 32-row tile only: the 64-row tile is the softmax probe's comparison
+    PSAMD_ROUTER_NB(32, true)
+  } else if (tm == 64) {
+    PSAMD_ROUTER_NB(64, false)
   } else {
-    PSAMD_ROUTER_NB(32)
+    PSAMD_ROUTER_NB(32, false)
   }
 #undef PSAMD_ROUTER_NB
 #undef PSAMD_ROUTER
@@ -390,7 +535,12 @@ void launch_moe_router_finish(const float* part, int nblk, int T, int E, int k, 
 
 void launch_moe_router_bwd(const float* logits, const float* lse, const int64_t* idx, const float* wts, const float* dwts,
                            const float* daux, const int* counts, int T, int E, int k, bool norm, float aux_coef,
-                           float z_coef, uint16_t* dz, hipStream_t st) {
+                           float z_coef, bool sigmoid, float scale, uint16_t* dz, hipStream_t st) {
+  if (sigmoid) {
+    hipLaunchKernelGGL(moe_router_sigmoid_bwd_kernel, dim3(stream_grid(static_cast<int64_t>(T) * 64, kNT)), dim3(kNT), 0,
+                       st, logits, lse, idx, wts, dwts, daux, counts, T, E, k, norm ? 1 : 0, aux_coef, z_coef, scale, dz);
+    return;
+  }
   hipLaunchKernelGGL(moe_router_bwd_kernel, dim3(stream_grid(static_cast<int64_t>(T) * 64, kNT)), dim3(kNT), 0, st,
                      logits, lse, idx, wts, dwts, daux, counts, T, E, k, norm ? 1 : 0, aux_coef, z_coef, dz);
 }

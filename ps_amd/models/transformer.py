@@ -25,7 +25,7 @@ from torch.utils.checkpoint import checkpoint
 from ..ops.dense import SplitKLinear
 from ..ops.linear import PsLinear
 from ..ops.lm_head import linear_cross_entropy
-from ..ops.moe import moe_ffn, route as moe_route, router as moe_router
+from ..ops.moe import moe_ffn, route as moe_route, router as moe_router, router_ok as moe_router_ok
 from ..ops.transformer import (PackedSeqs, attention_causal_gqa, attention_qkv, cross_entropy,
                               doc_bounds as _doc_bounds, layer_norm_residual, pack_seqs, rms_norm, rope_split,
                               rope_table, swiglu)
@@ -253,6 +253,15 @@ class LlamaConfig:
     moe_fused_router: bool = False
     moe_aux_coef: float = 0.0
     moe_z_coef: float = 0.0
+    # DeepSeek-V3 style routing (``router(score="sigmoid", ...)``): sigmoid scores, the k experts chosen inside the
+    # moe_topk_group best of moe_n_group expert groups, the weights times moe_route_scale.  moe_bias_balance: the
+    # choice is made on score + ``router_bias``, a buffer that ``update_router_bias`` moves from the load counts
+    # (aux-loss-free balancing).  Any non-default value selects ``router`` too
+    moe_score: str = "softmax"
+    moe_n_group: int = 1
+    moe_topk_group: int = 1
+    moe_route_scale: float = 1.0
+    moe_bias_balance: bool = False
     # with labels, the loss straight from the last hidden states and lm_head.weight, no [B*S, vocab] logits or
     # gradient in memory (ops/lm_head.py); opt-in: it trades time for that memory (profiles/lm_head_probe.txt)
     fused_head: bool = False
@@ -320,6 +329,9 @@ class LlamaBlock(nn.Module):
             self.router = nn.Linear(c.hidden, c.moe_experts, bias=False)
             self.w13_e = nn.Parameter(torch.empty(c.moe_experts, 2 * f, c.hidden).normal_(std=0.02))
             self.w2_e = nn.Parameter(torch.empty(c.moe_experts, c.hidden, f).normal_(std=0.02))
+            if c.moe_bias_balance:  # only then: other configs keep their state_dict keys
+                self.register_buffer("router_bias", torch.zeros(c.moe_experts, dtype=torch.float32))
+                self.last_counts = None  # this layer's per-expert pair counts of its last forward
         else:
             self.w13 = PsLinear(c.hidden, 2 * c.ffn, bias=False)
             self.w2 = PsLinear(c.ffn, c.hidden, bias=False)
@@ -356,9 +368,16 @@ class LlamaBlock(nn.Module):
         aux = None
         if c.moe_experts:  # routing on [T, E]; the experts on the grouped kernels (csrc/kernels/moe.hip)
             hf = h.reshape(b * s, c.hidden)
-            if c.moe_fused_router or c.moe_aux_coef or c.moe_z_coef:  # csrc/kernels/moe_router.hip
+            scoring = (c.moe_score, c.moe_n_group, c.moe_topk_group, c.moe_route_scale) != ("softmax", 1, 1, 1.0)
+            if c.moe_fused_router or c.moe_aux_coef or c.moe_z_coef or scoring or c.moe_bias_balance:
+                # csrc/kernels/moe_router.hip
                 idx, wts, aux = moe_router(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk, c.moe_aux_coef,
-                                           c.moe_z_coef)
+                                           c.moe_z_coef, score=c.moe_score, bias=getattr(self, "router_bias", None),
+                                           n_group=c.moe_n_group, topk_group=c.moe_topk_group, scale=c.moe_route_scale)
+                if c.moe_bias_balance:  # kept here: router.last_counts is overwritten by the next layer's call
+                    self.last_counts = moe_router.last_counts if moe_router_ok(hf, self.router.weight, c.moe_top_k) \
+                        else torch.zeros_like(self.router_bias, dtype=torch.int32).scatter_add_(
+                            0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.int32, device=idx.device))
             else:  # in torch
                 idx, wts = moe_route(hf, self.router.weight, c.moe_top_k, c.moe_norm_topk)
             out = moe_ffn(hf, idx, wts, self.w13_e, self.w2_e).view(b, s, c.hidden)
@@ -367,6 +386,14 @@ class LlamaBlock(nn.Module):
         if not with_aux:
             return x, out
         return x, out, torch.zeros((), dtype=torch.float32, device=x.device) if aux is None else aux
+
+    @torch.no_grad()
+    def update_router_bias(self, rate: float):
+        """Aux-loss-free balancing (``c.moe_bias_balance``): ``router_bias += rate * sign(mean(counts) - counts)``
+        with the counts of this layer's last forward -- up for under-loaded experts, down for over-loaded ones.
+        On the device, no host sync."""
+        counts = self.last_counts.float()  # the buffer follows the module's dtype; the comparison stays in fp32
+        self.router_bias.add_(torch.sign(counts.mean() - counts).to(self.router_bias.dtype), alpha=rate)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -382,6 +409,13 @@ class LlamaForCausalLM(nn.Module):
         for m in self.modules():
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
+
+    def update_router_bias(self, rate: float):
+        """``LlamaBlock.update_router_bias`` on every MoE layer (``c.moe_bias_balance``), after a forward."""
+        if not (self.c.moe_experts and self.c.moe_bias_balance):
+            raise ValueError("update_router_bias: a model without moe_bias_balance has no router bias")
+        for layer in self.layers:
+            layer.update_router_bias(rate)
 
     def forward(self, ids, labels=None, doc_ids=None):
         """``doc_ids`` [B, S] (any integer dtype): packed rows -- a new document begins wherever the id

@@ -5,7 +5,8 @@
 ``x`` [T, D] bf16, ``idx`` [T, k] integer expert ids in [0, E) (the k ids of a token distinct), ``wts`` [T, k] fp32,
 ``w13`` [E, 2F, D] (gate rows, then up rows, as ``LlamaBlock.w13``), ``w2`` [E, D, F].  Routing stays outside:
 ``route`` (router logits, softmax, topk, renormalisation and their autograd in torch, bf16 logits) or ``router``
-(one GEMM with the routing in its epilogue, fp32 logits, plus the load-balancing and z losses).
+(one GEMM with the routing in its epilogue, fp32 logits, plus the load-balancing and z losses; softmax scores, or
+sigmoid scores with a selection bias and a group-limited top-k).
 
 The fused route: ``moe_plan`` sorts the T * k (token, slot) pairs by expert into a row space in which every
 expert's segment starts at a multiple of the 128-row GEMM tile (R_cap rows, sized from T, k and E alone: no host
@@ -132,21 +133,54 @@ def route(h: torch.Tensor, router_weight: torch.Tensor, top_k: int, norm_topk: b
 
 
 # ----------------------------------------------------------------------------------- fused router (moe_router.hip)
+def _check_scoring(E: int, top_k: int, score: str, bias, n_group: int, topk_group: int, scale: float) -> None:
+    """``ValueError`` for scoring arguments outside ``router``'s definition."""
+    if score == "softmax":
+        if bias is not None or n_group != 1 or topk_group != 1 or scale != 1.0:
+            raise ValueError("router: bias, n_group, topk_group and scale belong to score='sigmoid'")
+    elif score != "sigmoid":
+        raise ValueError("router: score is 'softmax' or 'sigmoid'")
+    elif not 1 <= topk_group <= n_group <= 32 or E % n_group:
+        raise ValueError("router: E % n_group == 0 and 1 <= topk_group <= n_group <= 32")
+    elif top_k > topk_group * (E // n_group):
+        raise ValueError("router: top_k <= topk_group * E / n_group")
+    elif bias is not None and (tuple(bias.shape) != (E,) or bias.dtype not in (torch.float32, torch.bfloat16)):
+        raise ValueError("router: bias [E], fp32 or bf16")
+
+
 def _router_ref(h: torch.Tensor, w: torch.Tensor, top_k: int, norm_topk: bool = True, aux_coef: float = 0.0,
-                z_coef: float = 0.0, idx: Optional[torch.Tensor] = None):
+                z_coef: float = 0.0, idx: Optional[torch.Tensor] = None, *, score: str = "softmax",
+                bias: Optional[torch.Tensor] = None, n_group: int = 1, topk_group: int = 1, scale: float = 1.0):
     """The definition of ``router`` as a torch composition in the dtype of its inputs (bf16 inputs: the logits are a
     bf16 matmul output, as in ``route``; fp64 inputs: the high-precision reference).  ``idx`` overrides the top-k
     choice.  No host sync.  -> (idx, wts, aux)"""
+    E = w.shape[0]
+    _check_scoring(E, top_k, score, bias, n_group, topk_group, scale)
     z = F.linear(h, w)
     z = z.to(torch.promote_types(z.dtype, torch.float32))
     lse = torch.logsumexp(z, -1)
-    p = (z - lse[:, None]).exp()
-    if idx is None:  # descending, a tie to the lower id
-        idx = torch.sort(z, dim=-1, descending=True, stable=True).indices[:, :top_k]
-    wts = p.gather(1, idx)
+    if score == "sigmoid":
+        s = torch.sigmoid(z)
+        if idx is None:
+            c = s.detach() if bias is None else s.detach() + bias.detach().to(z.dtype)
+            if n_group > topk_group:  # the topk_group groups of largest (sum of their two largest c), a tie to the lower id
+                per = c.view(-1, n_group, E // n_group)
+                gscore = per.topk(min(2, E // n_group), dim=-1).values.sum(-1)
+                kept = torch.sort(gscore, dim=-1, descending=True, stable=True).indices[:, :topk_group]
+                drop = torch.ones_like(gscore, dtype=torch.bool).scatter_(1, kept, False)
+                c = per.masked_fill(drop[:, :, None], float("-inf")).view(-1, E)
+            idx = torch.sort(c, dim=-1, descending=True, stable=True).indices[:, :top_k]
+        wts = s.gather(1, idx)
+        p = s / s.sum(-1, keepdim=True)  # what the balance loss averages: DeepSeek-V3's normalised scores
+    else:
+        p = (z - lse[:, None]).exp()
+        if idx is None:  # descending, a tie to the lower id
+            idx = torch.sort(z, dim=-1, descending=True, stable=True).indices[:, :top_k]
+        wts = p.gather(1, idx)
     if norm_topk:
         wts = wts / wts.sum(-1, keepdim=True)
-    E = w.shape[0]
+    if score == "sigmoid":
+        wts = wts * scale
     flat = idx.reshape(-1)
     counts = torch.zeros(E, dtype=torch.int64, device=z.device).scatter_add_(0, flat, torch.ones_like(flat))
     lb = E * ((counts.to(z.dtype) / flat.numel()) * p.mean(0)).sum()  # f carries no gradient, P does
@@ -168,14 +202,20 @@ def router_ok(h: torch.Tensor, w: torch.Tensor, top_k: int) -> bool:
 
 class _Router(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, w, top_k, norm_topk, aux_coef, z_coef):
+    def forward(ctx, h, w, top_k, norm_topk, aux_coef, z_coef, score="softmax", bias=None, n_group=1, topk_group=1,
+                scale=1.0):
         """h [T, D], w [E, D] bf16 -> (idx, wts, aux, counts [E] int32)"""
         n = native()
         h, w = h.contiguous(), w.contiguous()
-        idx, wts, lse, logits, part = n.moe_router_fwd(h, w, top_k, norm_topk)
+        sig = score == "sigmoid"
+        if sig:
+            bias = None if bias is None else bias.detach().float().contiguous()
+            idx, wts, lse, logits, part = n.moe_router_fwd(h, w, top_k, norm_topk, 0, True, bias, n_group, topk_group, scale)
+        else:
+            idx, wts, lse, logits, part = n.moe_router_fwd(h, w, top_k, norm_topk)
         counts, _, stats = n.moe_router_finish(part, h.shape[0], top_k, aux_coef, z_coef)
         ctx.save_for_backward(h, w, logits, lse, idx, wts, counts)
-        ctx.args = (norm_topk, aux_coef, z_coef)
+        ctx.args = (norm_topk, aux_coef, z_coef, sig, scale)
         ctx.mark_non_differentiable(idx, counts)
         return idx, wts, stats[2], counts
 
@@ -187,11 +227,12 @@ class _Router(torch.autograd.Function):
         dz = native().moe_router_bwd(logits, lse, idx, wts, dwts, daux, counts, *ctx.args)  # [T, E] bf16
         dh = torch.mm(dz, w) if ctx.needs_input_grad[0] else None
         dw = torch.mm(dz.t(), h) if ctx.needs_input_grad[1] else None
-        return dh, dw, None, None, None, None
+        return (dh, dw) + (None,) * 9
 
 
 def router(h: torch.Tensor, router_weight: torch.Tensor, top_k: int, norm_topk: bool = True, aux_coef: float = 0.0,
-           z_coef: float = 0.0):
+           z_coef: float = 0.0, *, score: str = "softmax", bias: Optional[torch.Tensor] = None, n_group: int = 1,
+           topk_group: int = 1, scale: float = 1.0):
     """Router with fp32 logits and the auxiliary losses.  ``h`` [T, D], ``router_weight`` [E, D] ->
     (idx [T, k] int64: the k experts of largest logit, descending, a tie to the lower id; wts [T, k]: their softmax
     probabilities, renormalised over the k when ``norm_topk``; aux: ``aux_coef`` * load-balancing loss (Switch /
@@ -200,15 +241,25 @@ def router(h: torch.Tensor, router_weight: torch.Tensor, top_k: int, norm_topk: 
     (csrc/kernels/moe_router.hip), the logits never rounded below fp32; otherwise, and under
     PS_AMD_DISABLE=moe_router, ``_router_ref``.  ``router.last_counts`` holds the per-expert pair counts [E] int32 of
     the most recent fused call only: every call overwrites it, so with several MoE layers it is the last layer's, and
-    a recomputation under activation checkpointing writes it again.  Read it right after the call it belongs to."""
+    a recomputation under activation checkpointing writes it again.  Read it right after the call it belongs to.
+
+    ``score="sigmoid"`` (DeepSeek-V3 style; the other four keywords need it): the scores are ``s = sigmoid(z)``; the
+    k experts are those of largest ``s + bias`` (``bias`` [E] fp32 or bf16, no gradient, None: zeros) -- with
+    ``n_group > topk_group`` only among the ``topk_group`` groups of largest group score, a group being
+    ``E / n_group`` consecutive experts and its score the sum of its two largest ``s + bias``; ties go to the lower
+    id at both steps.  ``wts`` are the unbiased ``s`` of the chosen, renormalised when ``norm_topk``, times
+    ``scale``; the balance loss takes ``P_e = mean_t s[t, e] / sum_e' s[t, e']``; the z-loss is unchanged."""
     if h.dim() != 2 or router_weight.dim() != 2 or h.shape[1] != router_weight.shape[1]:
         raise ValueError("router: h [T, D], router_weight [E, D]")
     if not 1 <= top_k <= router_weight.shape[0]:
         raise ValueError("router: 1 <= top_k <= E")
+    n_group, topk_group, scale = int(n_group), int(topk_group), float(scale)
+    _check_scoring(router_weight.shape[0], top_k, score, bias, n_group, topk_group, scale)
     if not router_ok(h, router_weight, top_k):
-        return _router_ref(h, router_weight, top_k, norm_topk, aux_coef, z_coef)
+        return _router_ref(h, router_weight, top_k, norm_topk, aux_coef, z_coef, score=score, bias=bias, n_group=n_group,
+                           topk_group=topk_group, scale=scale)
     idx, wts, aux, router.last_counts = _Router.apply(h, router_weight, int(top_k), bool(norm_topk), float(aux_coef),
-                                                      float(z_coef))
+                                                      float(z_coef), score, bias, n_group, topk_group, scale)
     return idx, wts, aux
 
 
